@@ -18,16 +18,26 @@ A step (timed) = the whole read of the file by all ranks:
   * all_gather of the per-partition (count, digest) descriptors and the whole-file digest fold.
 Records stay in HBM.  value = the file's decompressed bytes / max-over-ranks step time.
 
-At N = 1 (rank 0 holds the whole file) the CPU baseline runs the oracle (CPU restatement of the
-same per-partition work, zlib inflate) on the box's usable cores over a bounded sample of the
-same partitions; its per-partition digests -- over every partition, the ones past the timed
-sample run once more untimed -- are compared with the GPU's ("parity" in the line; a mismatch
-exits non-zero).
+A plain run does only what the headline figure needs: it sets up the file, warms up, times the
+steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.  Everything else
+runs under --full, untimed and as before: at N = 1 (rank 0 holds the whole file) the end-to-end
+leg, the write path, the interval-filter leg and the CPU baseline, which runs the oracle (CPU
+restatement of the same per-partition work, zlib inflate) on the box's usable cores over a bounded
+sample of the same partitions; its per-partition digests -- over every partition, the ones past
+the timed sample run once more untimed -- are compared with the GPU's ("parity" in the line; a
+mismatch exits non-zero); at N > 1 the per-rank oracle parity of the shards.
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]; for N > 1 the driver uses
-torch.distributed.run, one rank per GPU (RCCL).
+The N = 1 file is a pure function of (shape, --gb, --seed, generator source), and generating it
+(zlib level 5 over ~36 GB) takes about a minute on 16 threads, so it is kept in
+disq_amd/_build/bench_input/ (one slot, not in git): `bench.py --prepare-input` writes it (called
+by __graft_entry__.build() where a GPU is present), and a run that finds no matching slot
+generates the file as before and fills the slot for the next run.
+
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--dump-outputs DIR] [--full]; for N > 1
+the driver uses torch.distributed.run, one rank per GPU (RCCL).
 """
 import argparse
+import hashlib
 import json
 import math
 import os
@@ -44,6 +54,9 @@ TRAFFIC_PROFILE = "r6z_inflate_traffic_pmc.json"
 # utilisation of K2 from PMC counters of the benched build (tools/pmc_summary.py over a
 # tools/pmc_inflate.sh run): VALU issue, LDS busy / bank-conflict / unaligned fractions
 UTIL_PROFILE = "r6z_inflate_util.json"
+# the N = 1 file between runs (one slot): input.bam, input.bai (WGS), key.json (written last)
+INPUT_DIR = os.path.join(ROOT, "disq_amd", "_build", "bench_input")
+UNPLACED_FRACTION = 0.005
 
 
 def log(*a):
@@ -82,10 +95,22 @@ def parse():
                     help="end-to-end export: lean = voffsets + raw record bytes (DQ_EXPORT_LEAN, "
                          "the fields are parsed from the raw bytes as BAMRecordCodec.decode does), "
                          "raw = also every SoA field, hash and raw offset")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs: end-to-end read, write path, interval filter, "
+                         "CPU baseline and the oracle parity checks (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (per-partition "
+                         "record counts and digests, the file's totals) as DIR/<name>.npy (float64)")
+    ap.add_argument("--prepare-input", action="store_true",
+                    help="generate the N = 1 file of these arguments into its slot under "
+                         "disq_amd/_build/bench_input/ and exit (no GPU work)")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="generation rehearsal: generate rank 0's share of an N-rank run under "
                          "the N-rank thread budget, report the time as JSON and exit (no GPU work)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cores():
@@ -116,7 +141,9 @@ def main():
     rehearsal = os.environ.get("DQ_BENCH_REHEARSAL") == "1"
     if rehearsal:
         local = 0
-    if not args.emulate_world:
+    if args.prepare_input and (world > 1 or args.emulate_world):
+        raise SystemExit("--prepare-input prepares the N = 1 file: run it as one process")
+    if not args.emulate_world and not args.prepare_input:
         torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     cdev = torch.device("cpu") if rehearsal else dev  # where collective tensors live
@@ -145,7 +172,16 @@ def main():
     n_total = int(args.gb * 1e9 / per_rec) * gworld
     nchunks = synth.chunk_count(n_total, shape=shape)
     k0, k1 = rank * nchunks // gworld, (rank + 1) * nchunks // gworld
-    want_bai = gworld == 1 and args.intervals > 0 and shape == synth.WGS
+    want_bai = gworld == 1 and args.full and args.intervals > 0 and shape == synth.WGS
+    # the N = 1 file's slot (module docstring); its .bai is kept with it whether or not this run
+    # asks for it, so the slot serves plain and --full runs alike
+    key = input_key(args, n_total) if gworld == 1 else None
+    keep_bai = shape == synth.WGS
+    if args.prepare_input and slot_matches(key):
+        print(json.dumps({"prepared": os.path.relpath(INPUT_DIR, ROOT), "key": key,
+                          "already": True}), flush=True)
+        return
+    cached = load_input(key, want_bai, gen_threads) if key else None
     # Generation budget: zlib level 5 (htsjdk's) costs ~1 thread-second per chunk, so with few
     # threads per rank (an 8-GPU node under a small CPU quota) the ranks generate a pool of
     # distinct chunks and tile it over their byte range (the blocks are the same level-5 BGZF
@@ -158,22 +194,38 @@ def main():
     log(f"[bench] rank {rank}: chunks [{k0}, {k1}) of {nchunks} ({n_total} records in the file), "
         f"{gen_threads} threads, estimated {est:.0f} s" + (f", pool of {pool} chunks" if pool else ""))
     import ctypes
-    if pool is None or pool >= k1 - k0:
+    bai = None
+    if cached is not None:
+        own_np, bai = cached
+        own_len, free = len(own_np), (lambda: None)
+        gen_desc = {"distinct_chunks": k1 - k0, "tiled_chunks": 0, "from_slot": True}
+    elif pool is None or pool >= k1 - k0:
         res, free = synth.generate(n_total, seed=args.seed, nthreads=gen_threads, as_buffer=True,
-                                   bai=want_bai, unplaced_fraction=0.005, shape=shape,
+                                   bai=want_bai or (key is not None and keep_bai),
+                                   unplaced_fraction=UNPLACED_FRACTION, shape=shape,
                                    chunks=None if gworld == 1 else (k0, k1))
         own_len = res.bam_len
         own_np = np.ctypeslib.as_array((ctypes.c_uint8 * own_len).from_address(res.bam))
+        if res.bai:
+            bai = bytes((ctypes.c_uint8 * res.bai_len).from_address(res.bai))
         gen_desc = {"distinct_chunks": k1 - k0, "tiled_chunks": 0}
+        if key is not None:
+            store_input(key, own_np, bai)
+        if not want_bai:
+            bai = None
     else:
         own_np, free = tiled_rank_bytes(synth, n_total, args.seed, gen_threads, k0, k1, nchunks,
                                         pool, shape)
         own_len = len(own_np)
-        res = None
         gen_desc = {"distinct_chunks": pool + (1 if k0 == 0 else 0),
                     "tiled_chunks": (k1 - k0) - pool - (1 if k0 == 0 else 0),
                     "note": "a pool of distinct level-5 chunks tiled over the rank's range"}
     gen_s = time.time() - t0
+    if args.prepare_input:
+        free()
+        print(json.dumps({"prepared": os.path.relpath(INPUT_DIR, ROOT), "key": key,
+                          "bytes": own_len, "seconds": round(gen_s, 1)}), flush=True)
+        return
     if args.emulate_world:
         free()
         print(json.dumps({
@@ -213,7 +265,7 @@ def main():
     # measured 1.00 s against 0.77-0.81 s in a fresh process, every stage slower
     # (profiles/r6b_e2e_sweep.txt); its digest is compared with the resident run's below
     e2e = None
-    if world == 1 and args.e2e:
+    if world == 1 and args.full and args.e2e:
         e2e = end_to_end(own_np, args, None, header)
     # resident own bytes (H2D, outside the timed region)
     t0 = time.time()
@@ -221,8 +273,7 @@ def main():
     rs.reserve(0)
     torch.cuda.synchronize()
     h2d_s = time.time() - t0
-    bai = ctypes.string_at(res.bai, res.bai_len) if (want_bai and res is not None and res.bai) else None
-    cpu_data = own_np.copy() if (world == 1 and args.cpu_seconds > 0) else None
+    cpu_data = own_np.copy() if (world == 1 and args.full and args.cpu_seconds > 0) else None
     own_host = torch.from_numpy(own_np.copy()) if (rehearsal and world > 1) else None
     del own_np
     free()
@@ -269,10 +320,13 @@ def main():
             every = d[None]
         if int(every[:, 0].max()) != 0:
             return None
+        counts = np.zeros(nsplit, dtype=np.int64)
         digests = np.zeros(nsplit, dtype=np.uint64)
         for r, s in enumerate(plan):
+            counts[s.p0:s.p1] = every[r, 3:3 + s.p1 - s.p0]
             digests[s.p0:s.p1] = every[r, 3 + maxp:3 + maxp + s.p1 - s.p0].view(np.uint64)
-        return st, int(every[:, 1].sum()), int(every[:, 2].sum()), P.fold_digest_np(digests)
+        return (st, int(every[:, 1].sum()), int(every[:, 2].sum()), P.fold_digest_np(digests),
+                counts, digests)
 
     def barrier():
         torch.cuda.synchronize()
@@ -300,7 +354,7 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     ms_step = el * 1e3 / args.steps
-    stats, ubytes, nrec, digest = outs[-1]
+    stats, ubytes, nrec, digest, part_counts, part_digests = outs[-1]
     comp_bytes = file_len  # C of the whole job (every rank's shard)
     for i, o in enumerate(outs):
         log(f"[bench] step {i}: {o[0].ms_total:.1f} ms device (scan {o[0].ms_scan:.1f}, inflate "
@@ -339,7 +393,9 @@ def main():
     interval_mode = cpu = parity = wpath = None
     if e2e is not None and "digest" in e2e:
         e2e["digest_match"] = e2e["digest"] == f"{digest:016x}"
-    if world == 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, part_counts, part_digests, ubytes, nrec, digest)
+    if world == 1 and args.full:
         if args.write_records > 0:
             wpath = write_path_bench(args)
         if bai is not None:
@@ -347,16 +403,17 @@ def main():
                                            ncores)
         if cpu_data is not None:
             cpu, parity = cpu_baseline(cpu_data, ctx, rs, shard, file_len, header, args, ncores)
-    if world > 1:
+    if world > 1 and args.full:
         # every rank, untimed: the oracle over the bytes it decoded (resident + halo received in
         # the timed steps), its owned partitions vs the GPU's descriptors of the last timed step
         parity = shard_parity(rs, shard, offsets, rank, file_len, header, args.split_size, ctx,
                               dist, cdev, world, max(1, ncores // max(1, local_world)))
-    if rehearsal and world > 1 and rank == 0 and not pool:
+    if rehearsal and args.full and world > 1 and rank == 0 and not pool:
         # the whole logical file, generated at once, through the oracle: its digest must equal
         # the digest folded from the shards
         from oracle import oracle as O
-        whole = synth.generate(n_total, seed=args.seed, nthreads=gen_threads, unplaced_fraction=0.005)
+        whole = synth.generate(n_total, seed=args.seed, nthreads=gen_threads,
+                               unplaced_fraction=UNPLACED_FRACTION)
         _, odig, _ = O.run_partitions(whole.bam, O.path_splits(len(whole.bam), args.split_size),
                                       ncores)
         ok = len(whole.bam) == file_len and P.fold_digest([int(x) for x in odig]) == digest
@@ -375,6 +432,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_step, 3),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -450,6 +508,101 @@ def main():
         sys.exit(3)
     if (interval_mode or {}).get("parity") and interval_mode["parity"].get("status") != "match":
         sys.exit(3)
+
+
+def dump_outputs(out_dir, counts, digests, ubytes, nrec, digest):
+    """--dump-outputs: what the last timed step returned, as float64 .npy files (a few KB).  A
+    64-bit digest does not fit a float64, so each is written as four 16-bit limbs, most
+    significant first: every value is an exact integer and any change moves a limb by >= 1."""
+    import numpy as np
+
+    def limbs(x):
+        x = np.atleast_1d(np.asarray(x, dtype=np.uint64))
+        return np.stack([(x >> np.uint64(s)) & np.uint64(0xFFFF) for s in (48, 32, 16, 0)],
+                        axis=-1).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "partition_records.npy"), counts.astype(np.float64))
+    np.save(os.path.join(out_dir, "partition_digests.npy"), limbs(digests))
+    # [decompressed bytes, records, the four limbs of the whole-file digest]
+    np.save(os.path.join(out_dir, "file_totals.npy"),
+            np.concatenate([np.array([ubytes, nrec], np.float64), limbs(digest)[0]]))
+
+
+def input_key(args, n_total):
+    """What the N = 1 file is a function of (the generator's source stands in for its version)."""
+    h = hashlib.sha256()
+    for rel in ("disq_amd/csrc/synth_bam.cpp", "include/disq_synth.h"):
+        with open(os.path.join(ROOT, rel), "rb") as f:
+            h.update(f.read())
+    return {"shape": args.shape, "gb": args.gb, "seed": args.seed, "records": n_total,
+            "unplaced_fraction": UNPLACED_FRACTION, "generator_sha256": h.hexdigest()}
+
+
+def slot_matches(key):
+    try:
+        with open(os.path.join(INPUT_DIR, "key.json")) as f:
+            return json.load(f) == key
+    except (OSError, ValueError):
+        return False
+
+
+def load_input(key, want_bai, threads):
+    """(file bytes as a uint8 array, .bai bytes or None) from the slot, or None if it holds another
+    file.  The bytes are read by `threads` pread threads (a page-cached 12.5 GB on 16 threads:
+    well under a second)."""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    if not slot_matches(key):
+        return None
+    try:
+        path = os.path.join(INPUT_DIR, "input.bam")
+        n = os.path.getsize(path)
+        buf = np.empty(n, np.uint8)
+        mv = memoryview(buf)
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            def part(i):
+                lo, hi = i * n // threads, (i + 1) * n // threads
+                while lo < hi:
+                    got = os.preadv(fd, [mv[lo:min(hi, lo + (64 << 20))]], lo)
+                    if got <= 0:
+                        raise OSError(f"{path}: short read at {lo}")
+                    lo += got
+            with ThreadPoolExecutor(threads) as ex:
+                list(ex.map(part, range(threads)))
+        finally:
+            os.close(fd)
+        bai = None
+        if want_bai:
+            with open(os.path.join(INPUT_DIR, "input.bai"), "rb") as f:
+                bai = f.read()
+        log(f"[bench] the file ({n / 1e9:.2f} GB) read from {os.path.relpath(INPUT_DIR, ROOT)}")
+        return buf, bai
+    except OSError as e:
+        log(f"[bench] input slot unreadable ({e}); generating")
+        return None
+
+
+def store_input(key, data, bai):
+    """Fill the slot; key.json goes last, so a half-written slot never matches.  A full disk only
+    costs the next run its shortcut."""
+    try:
+        os.makedirs(INPUT_DIR, exist_ok=True)
+        kp = os.path.join(INPUT_DIR, "key.json")
+        if os.path.exists(kp):
+            os.unlink(kp)
+        data.tofile(os.path.join(INPUT_DIR, "input.bam"))
+        with open(os.path.join(INPUT_DIR, "input.bai"), "wb") as f:
+            f.write(bai or b"")
+        with open(kp, "w") as f:
+            json.dump(key, f)
+    except OSError as e:
+        log(f"[bench] could not keep the file in {os.path.relpath(INPUT_DIR, ROOT)}: {e}")
+        for name in ("key.json", "input.bam", "input.bai"):
+            try:
+                os.unlink(os.path.join(INPUT_DIR, name))
+            except OSError:
+                pass
 
 
 def shard_parity(rs, shard, offsets, rank, file_len, header, split_size, ctx, dist, cdev, world,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU call for a kernel-variant round: the inflate parity tests under each variant library,
 # the interleaved A/B of the product library against them (tools/gpu_variant_ab.sh), then the
-# whole -m gpu suite and the default bench line on the product library.  Stops at the first
+# whole -m gpu suite and the default bench.py --full line on the product library.  Stops at the first
 # failure.  usage: tools/gpu_ab_then_suite.sh TAG [VARIANT_LIB...]   (names under disq_amd/_build)
 set -eo pipefail
 tag=$1; shift
@@ -20,7 +20,7 @@ tail -1 $out/smoke.log
 timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
   > $out/gpu_tests.log 2>&1 || { tail -40 $out/gpu_tests.log; exit 1; }
 tail -1 $out/gpu_tests.log
-timeout -k 10 600 python3 -u bench.py > $out/bench_default.log 2>&1
+timeout -k 10 600 python3 -u bench.py --full > $out/bench_default.log 2>&1
 grep '"metric"' $out/bench_default.log | tail -1 > $out/bench_default.json
 python3 -c "
 import json; d=json.load(open('$out/bench_default.json')); c=d['config']
