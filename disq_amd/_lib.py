@@ -113,7 +113,7 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_text_open_path", "dq_text_run", "dq_text_read", "dq_text_batch_free",
            "dq_bgzf_compress", "dq_bgzf_compress_resident", "dq_bgzf_fetch",
            "dq_text_set_index", "dq_text_set_intervals", "dq_decode_file_multi",
-           "dq_set_export_arena", "dq_checked_report", "dq_abi_version")
+           "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai")
 
 _lib = None
 _lock = threading.Lock()
@@ -147,6 +147,7 @@ def lib():
         L.dq_set_index.argtypes = [vp, vp, C.c_int64]
         L.dq_set_splitting_index.argtypes = [vp, vp, C.c_int64, C.c_int32]
         L.dq_write_sbi.argtypes = [vp, C.c_int64, P(P(C.c_uint8)), P(C.c_int64)]
+        L.dq_write_bai.argtypes = [vp, P(P(C.c_uint8)), P(C.c_int64), P(C.c_double)]
         L.dq_open_shard.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                     vp, C.c_int64]
         L.dq_open_shard_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
@@ -532,6 +533,21 @@ class Context:
         out = _copy_out(C.cast(p, C.c_void_p).value, n.value)
         lib().dq_free(C.cast(p, C.c_void_p))
         return out
+
+    def write_bai(self):
+        """BAMIndexer.createIndex of the open file (dq_write_bai): the .bai file's bytes.  The
+        device time of the index build alone is kept in `bai_ms` (see write_bai_timed)."""
+        return self.write_bai_timed()[0]
+
+    def write_bai_timed(self):
+        """(.bai bytes, device ms of the index build after the record pipeline)."""
+        p = C.POINTER(C.c_uint8)()
+        n, ms = C.c_int64(), C.c_double()
+        check(self._h, lib().dq_write_bai(self._h, C.byref(p), C.byref(n), C.byref(ms)))
+        out = _copy_out(C.cast(p, C.c_void_p).value, n.value)
+        lib().dq_free(C.cast(p, C.c_void_p))
+        self.bai_ms = ms.value
+        return out, ms.value
 
     def header(self):
         info = DqHeaderInfo()

@@ -2805,6 +2805,32 @@ int dq_set_splitting_index(dq_ctx* ctx, const uint8_t* sbi, int64_t len, int32_t
   return 0;
 }
 
+// finish(finalVirtualOffset): the file pointer after the last record (or after the header) of an
+// indexer-mode run, normalised as BlockCompressedInputStream.getFilePointer does: a consumed block
+// points to the next block's start (the EOF block, or the file end)
+static int final_pointer(dq_ctx* ctx, uint64_t* out) {
+  const int64_t nrec = ctx->nrec;
+  int64_t E = ctx->header_bytes;
+  if (nrec) {
+    int64_t lin = 0;
+    int32_t bs = 0;
+    HIPCHK(hipMemcpy(&lin, ctx->rec_lin.as<int64_t>() + nrec - 1, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&bs, ctx->f_bs.as<int32_t>() + nrec - 1, 4, hipMemcpyDeviceToHost));
+    E = lin + 4 + (int64_t)bs;
+  }
+  std::vector<int64_t> uo((size_t)ctx->nblk + 1), bp((size_t)ctx->nblk);
+  HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
+  uint64_t fin = (uint64_t)ctx->flen << 16;
+  if (E > 0) {
+    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end() - 1, E - 1) - uo.begin()) - 1;
+    if (j >= 0 && E < uo[(size_t)j + 1]) fin = ((uint64_t)bp[(size_t)j] << 16) | (uint64_t)(E - uo[(size_t)j]);
+    else if (j + 1 < ctx->nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
+  }
+  *out = fin;
+  return 0;
+}
+
 int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_len) {
   if (!ctx || !out || !out_len) return DQ_EINVAL;
   ON_DEVICE(ctx);
@@ -2825,26 +2851,8 @@ int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_l
     HIPCHK(hipMemcpyAsync(ent.data(), d.p, 8 * (size_t)nent, hipMemcpyDeviceToHost, ctx->s));
     HIPCHK(hipStreamSynchronize(ctx->s));
   }
-  // finish(finalVirtualOffset): the file pointer after the last record (or after the header),
-  // normalised as BlockCompressedInputStream.getFilePointer does: a consumed block points to the
-  // next block's start (the EOF block, or the file end)
-  int64_t E = ctx->header_bytes;
-  if (nrec) {
-    int64_t lin = 0;
-    int32_t bs = 0;
-    HIPCHK(hipMemcpy(&lin, ctx->rec_lin.as<int64_t>() + nrec - 1, 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&bs, ctx->f_bs.as<int32_t>() + nrec - 1, 4, hipMemcpyDeviceToHost));
-    E = lin + 4 + (int64_t)bs;
-  }
-  std::vector<int64_t> uo((size_t)ctx->nblk + 1), bp((size_t)ctx->nblk);
-  HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
-  uint64_t fin = (uint64_t)ctx->flen << 16;
-  if (E > 0) {
-    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end() - 1, E - 1) - uo.begin()) - 1;
-    if (j >= 0 && E < uo[(size_t)j + 1]) fin = ((uint64_t)bp[(size_t)j] << 16) | (uint64_t)(E - uo[(size_t)j]);
-    else if (j + 1 < ctx->nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
-  }
+  uint64_t fin = 0;
+  if ((rc = final_pointer(ctx, &fin))) return rc;
   ent[(size_t)nent] = fin;
   // SBIIndexWriter.finish (SBIIndexWriter.java:120-151): magic, file length, MD5, UUID, record
   // count, granularity, offset count, offsets (all little-endian)
@@ -2860,6 +2868,167 @@ int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_l
   for (size_t i = 0; i < ent.size(); i++) w64(68 + 8 * (int64_t)i, ent[i]);
   *out = b;
   *out_len = n;
+  return 0;
+}
+
+// BAMIndexer / BinningIndexBuilder: keys, linear index, level partition, bin and
+// chunk heads and the emit pass on the device; the host orders the bin headers and serialises.
+int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
+  if (!ctx || !out || !out_len) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  if (ctx->shard) RET(DQ_EINVAL, "dq_write_bai indexes a whole file, not a shard");
+  ctx->have_pipeline = false;
+  ctx->index_only = true;
+  int rc = run_pipeline(ctx);
+  ctx->index_only = false;
+  ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
+  if (rc) return rc;
+  if (ms) *ms = 0;
+  const int64_t n = ctx->nrec;
+  const int32_t n_ref = ctx->n_ref;
+  hipStream_t s = ctx->s;
+  if (n > INT32_MAX) RET(DQ_EINVAL, "dq_write_bai: more than 2147483647 records");
+  uint64_t fin = 0;
+  if ((rc = final_pointer(ctx, &fin))) return rc;
+  struct Ev {
+    hipEvent_t e = nullptr;
+    ~Ev() {
+      if (e) (void)hipEventDestroy(e);
+    }
+  } e0, e1;
+  HIPCHK(hipEventCreate(&e0.e));
+  HIPCHK(hipEventCreate(&e1.e));
+  HIPCHK(hipEventRecord(e0.e, s));
+  // hd: status, n_no_coor, then 5 words per reference (launch_bai_keys)
+  std::vector<unsigned long long> hd(2 + 5 * (size_t)n_ref, 0);
+  hd[0] = ~0ull;
+  DevBuf d_hd, d_key, d_end, d_span, d_woff, d_lin, d_in, d_sc, d_perm, d_chunks, d_bins;
+  const uint64_t* voff = ctx->f_voff.as<uint64_t>();
+  if (n) {
+    HIPCHK(d_hd.ensure(8 * hd.size()));
+    HIPCHK(d_key.ensure(8 * (size_t)n));
+    HIPCHK(d_end.ensure(4 * (size_t)n));
+    HIPCHK(hipMemcpyAsync(d_hd.p, hd.data(), 8 * hd.size(), hipMemcpyHostToDevice, s));
+    launch_bai_keys(ctx->U.as<uint8_t>(), ctx->rec_lin.as<int64_t>(), ctx->soa(), n, n_ref,
+                    d_key.as<uint64_t>(), d_end.as<int32_t>(), d_hd.as<unsigned long long>() + 2,
+                    d_hd.as<unsigned long long>(), d_hd.as<unsigned long long>() + 1, s);
+    HIPCHK(hipMemcpyAsync(hd.data(), d_hd.p, 8 * hd.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  if (hd[0] != ~0ull) {
+    const std::string at = "record " + std::to_string((long long)(hd[0] >> 8));
+    switch ((int)(hd[0] & 0xff)) {
+      case BAI_ST_REF: RET(DQ_EFORMAT, at + ": reference index beyond the header's references");
+      case BAI_ST_END: RET(DQ_EFORMAT, at + ": alignment end beyond 2^29, the .bai limit");
+      default: RET(DQ_EFORMAT, "not coordinate sorted: " + at + " is out of order");
+    }
+  }
+  const int64_t no_coor = (int64_t)hd[1], np = n - no_coor;
+  std::vector<int64_t> woff((size_t)n_ref + 1, 0);
+  for (int32_t r = 0; r < n_ref; r++) woff[(size_t)r + 1] = woff[(size_t)r] + (int64_t)hd[2 + 5 * (size_t)r + 4];
+  const int64_t nwin = woff[(size_t)n_ref];
+  int64_t nchunk = 0, nbin = 0;
+  std::vector<uint64_t> lin((size_t)nwin), chunks, bins, span(2 * (size_t)n_ref, 0);
+  if (np > 0) {
+    HIPCHK(d_span.ensure(8 * span.size()));
+    launch_bai_refspan(d_hd.as<unsigned long long>() + 2, n_ref, voff, n, fin, d_span.as<uint64_t>(), s);
+    // linear index
+    HIPCHK(d_woff.ensure(8 * woff.size()));
+    HIPCHK(d_lin.ensure(8 * (size_t)nwin));
+    HIPCHK(hipMemcpyAsync(d_woff.p, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_lin.p, 0xff, 8 * (size_t)nwin, s));
+    launch_bai_linear(d_key.as<uint64_t>(), d_end.as<int32_t>(), ctx->f_pos.as<int32_t>(), voff, n,
+                      d_woff.as<int64_t>(), nwin, d_lin.as<unsigned long long>(), s);
+    // the records of one bin level are a sorted subsequence: stable partition by level
+    if ((rc = ensure_scan(ctx, n))) return rc;
+    HIPCHK(d_in.ensure(8 * (size_t)n));
+    HIPCHK(d_sc.ensure(8 * ((size_t)n + 1)));
+    HIPCHK(d_perm.ensure(8 * (size_t)np));
+    int64_t base = 0;
+    for (int la = 0; la < 6; la += 2) {
+      launch_bai_level_flags(d_key.as<uint64_t>(), n, la, d_in.as<int64_t>(), s);
+      launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
+      int64_t tot = 0;
+      if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
+      const int64_t a = tot & 0xffffffff, b = tot >> 32;
+      launch_bai_level_scatter(d_key.as<uint64_t>(), n, la, d_sc.as<int64_t>(), base, base + a, np,
+                               d_perm.as<int64_t>(), s);
+      base += a + b;
+    }
+    if (base != np) RET(DQ_EDEVICE, "dq_write_bai: level partition lost records");
+    // bin and chunk heads, their scan, the emit pass
+    launch_bai_heads(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), np, d_in.as<int64_t>(), s);
+    launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), np, ctx->tmp.as<int64_t>(), s);
+    int64_t tot = 0;
+    if ((rc = get_i64(ctx, d_sc.as<int64_t>() + np, &tot))) return rc;
+    nchunk = tot & 0xffffffff;
+    nbin = tot >> 32;
+    HIPCHK(d_chunks.ensure(16 * (size_t)nchunk));
+    HIPCHK(d_bins.ensure(16 * (size_t)nbin));
+    launch_bai_emit(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), np, d_in.as<int64_t>(),
+                    d_sc.as<int64_t>(), nchunk, nbin, d_chunks.as<uint64_t>(), d_bins.as<uint64_t>(), s);
+    chunks.resize(2 * (size_t)nchunk);
+    bins.resize(2 * (size_t)nbin);
+    HIPCHK(hipMemcpyAsync(chunks.data(), d_chunks.p, 8 * chunks.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(bins.data(), d_bins.p, 8 * bins.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(span.data(), d_span.p, 8 * span.size(), hipMemcpyDeviceToHost, s));
+    if (nwin) HIPCHK(hipMemcpyAsync(lin.data(), d_lin.p, 8 * lin.size(), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipEventRecord(e1.e, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ms) *ms = ev_ms(e0.e, e1.e);
+  // bin headers into ascending (ref, bin); a bin's chunk count runs to the next head in device order
+  std::vector<int64_t> order((size_t)nbin);
+  for (int64_t b = 0; b < nbin; b++) order[(size_t)b] = b;
+  std::sort(order.begin(), order.end(),
+            [&](int64_t x, int64_t y) { return bins[2 * (size_t)x] < bins[2 * (size_t)y]; });
+  std::vector<uint8_t> o;
+  auto p32 = [&](uint32_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
+  auto p64 = [&](uint64_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 8); };
+  o.insert(o.end(), {'B', 'A', 'I', 1});
+  p32((uint32_t)n_ref);
+  size_t bi = 0;
+  for (int32_t r = 0; r < n_ref; r++) {
+    const unsigned long long* m = hd.data() + 2 + 5 * (size_t)r;
+    size_t bj = bi;
+    while (bj < order.size() && (int64_t)(bins[2 * (size_t)order[bj]] >> 16) == r) bj++;
+    const bool any = m[1] != 0;
+    p32((uint32_t)(bj - bi) + (any ? 1 : 0));
+    for (; bi < bj; bi++) {
+      const int64_t b = order[bi];
+      const int64_t c0 = (int64_t)bins[2 * (size_t)b + 1];
+      const int64_t c1 = b + 1 < nbin ? (int64_t)bins[2 * (size_t)b + 3] : nchunk;
+      p32((uint32_t)(bins[2 * (size_t)b] & 0xffff));
+      p32((uint32_t)(c1 - c0));
+      for (int64_t c = c0; c < c1; c++) {
+        p64(chunks[2 * (size_t)c]);
+        p64(chunks[2 * (size_t)c + 1]);
+      }
+    }
+    if (any) {  // pseudo-bin 37450: the reference's span, its mapped / unmapped counts
+      p32(37450);
+      p32(2);
+      p64(span[2 * (size_t)r]);
+      p64(span[2 * (size_t)r + 1]);
+      p64(m[2]);
+      p64(m[3]);
+    }
+    // linear index: an untouched window takes the previous window's offset (leading ones stay 0)
+    const int64_t ni = woff[(size_t)r + 1] - woff[(size_t)r];
+    p32((uint32_t)ni);
+    uint64_t prev = 0;
+    for (int64_t w = 0; w < ni; w++) {
+      const uint64_t v = lin[(size_t)(woff[(size_t)r] + w)];
+      if (v != ~0ull) prev = v;
+      p64(prev);
+    }
+  }
+  p64((uint64_t)no_coor);
+  uint8_t* b = (uint8_t*)malloc(o.size());
+  if (!b) return DQ_ENOMEM;
+  memcpy(b, o.data(), o.size());
+  *out = b;
+  *out_len = (int64_t)o.size();
   return 0;
 }
 

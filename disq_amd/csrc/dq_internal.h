@@ -42,6 +42,7 @@ enum : int {
   CHK_Z_STAGE = 11,  // deflate: a staged symbol word outside its lane's staging
   CHK_Z_IMAGE = 12,  // deflate: an emitted word outside the LDS deflate image
   CHK_K3_SPEC = 13,  // K3: the LDS-filtered segment speculation differs from seg_spec_kernel<64>
+  CHK_BAI = 14,      // .bai build: a linear window, perm slot, chunk or bin outside its table
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -249,6 +250,37 @@ void launch_sbi_sample(const uint64_t* voffset, int64_t nrec, int64_t g, uint64_
 void launch_partition_ranges(const SplitPlan* plans, int64_t nsplit, const int64_t* rec_lin,
                              const uint64_t* voffset, int64_t nrec, PartRange* parts,
                              int32_t* d_status, hipStream_t s);
+
+// .bai index build (dq_write_bai) over the n resident records.
+constexpr uint64_t BAI_UNPLACED = ~0ull;  // key of a record without coordinates
+enum : int { BAI_ST_REF = 1, BAI_ST_END = 2, BAI_ST_UNSORTED = 3 };  // *status & 0xff
+// key[i] = ref << 16 | bin, endp[i] = exclusive alignment end; *status (all ones) takes the first
+// offender (index << 8 | BAI_ST_*), *no_coor (zero) the unplaced count; meta (zero): 5 words per
+// reference = ~(first record), last record + 1, mapped, unmapped, last linear window + 1.
+void launch_bai_keys(const uint8_t* U, const int64_t* rec_lin, const RecSoA soa, int64_t n,
+                     int32_t n_ref, uint64_t* key, int32_t* endp, unsigned long long* meta,
+                     unsigned long long* status, unsigned long long* no_coor, hipStream_t s);
+// lin (all ones; nwin entries, reference r at win_off[r]): min voffset per 16 kb window
+void launch_bai_linear(const uint64_t* key, const int32_t* endp, const int32_t* pos,
+                       const uint64_t* voff, int64_t n, const int64_t* win_off, int64_t nwin,
+                       unsigned long long* lin, hipStream_t s);
+// span[2 r], [2 r + 1] = start of reference r's first record, end of its last (pseudo-bin 37450)
+void launch_bai_refspan(const unsigned long long* meta, int32_t n_ref, const uint64_t* voff,
+                        int64_t n, uint64_t fin, uint64_t* span, hipStream_t s);
+// Stable partition by bin level, levels la and la + 1 per pass: out[i] = (level == la) |
+// (level == la + 1) << 32 for the packed scan; perm[base + rank] = i from that scan.
+void launch_bai_level_flags(const uint64_t* key, int64_t n, int la, int64_t* out, hipStream_t s);
+void launch_bai_level_scatter(const uint64_t* key, int64_t n, int la, const int64_t* scan,
+                              int64_t base_a, int64_t base_b, int64_t nplaced, int64_t* perm,
+                              hipStream_t s);
+// out[j] = (record perm[j] opens a chunk) | (opens a bin) << 32; fin = the final file pointer
+void launch_bai_heads(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
+                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s);
+// chunks[2 c], [2 c + 1] = begin, end; bins[2 b], [2 b + 1] = key, first chunk
+void launch_bai_emit(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
+                     const int64_t* perm, int64_t nplaced, const int64_t* heads,
+                     const int64_t* scan, int64_t nchunk, int64_t nbin, uint64_t* chunks,
+                     uint64_t* bins, hipStream_t s);
 void launch_bs_plus4(const int32_t* bs, int64_t n, int32_t* out, hipStream_t s);
 void launch_add_u64(const uint64_t* in, int64_t n, uint64_t add, uint64_t* out, hipStream_t s);
 void launch_partition_digest2(const uint64_t* hash, PartRange* parts, int64_t nparts,

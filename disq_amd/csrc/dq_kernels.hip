@@ -1591,6 +1591,24 @@ __global__ __launch_bounds__(256) void partition_digest_kernel(const uint64_t* _
 // optimized (sorted, merged) QueryIntervals: a record matches iff an interval on its reference
 // has start <= alignmentEnd and end >= alignmentStart.  alignmentEnd = pos + refLen(CIGAR
 // M/D/N/=/X) for mapped reads, alignmentStart for unmapped reads with a position, 0 otherwise.
+
+// Reference length of record i (at U[p]): the sum of its M/D/N/=/X CIGAR op lengths; 0 when the
+// CIGAR does not fit in block_size.  Shared by kernel 4 and the .bai keys kernel.
+__device__ inline int32_t cigar_ref_len(const uint8_t* __restrict__ U, int64_t p, const RecSoA& soa,
+                                        int64_t i) {
+  const int64_t cp = p + 36 + soa.l_read_name[i];
+  const int nc = soa.n_cigar[i];
+  int32_t rl = 0;
+  if (32 + (int64_t)soa.l_read_name[i] + 4 * (int64_t)nc <= soa.block_size[i]) {
+    for (int c = 0; c < nc; c++) {
+      uint32_t op = (uint32_t)ld32(U, cp + 4 * c);
+      uint32_t o = op & 0xf;
+      if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rl += (int32_t)(op >> 4);
+    }
+  }
+  return rl;
+}
+
 __global__ __launch_bounds__(256) void interval_filter_kernel(
     const uint8_t* __restrict__ U, const int64_t* __restrict__ rec_lin, RecSoA soa,
     const int64_t* __restrict__ idx, int64_t n, const int32_t* __restrict__ iv_ref,
@@ -1608,18 +1626,7 @@ __global__ __launch_bounds__(256) void interval_filter_kernel(
     if (flag & 4) {
       aend = astart != 0 ? astart : 0;
     } else {
-      const int64_t p = rec_lin[i];
-      const int64_t cp = p + 36 + soa.l_read_name[i];
-      const int nc = soa.n_cigar[i];
-      int32_t rl = 0;
-      if (32 + (int64_t)soa.l_read_name[i] + 4 * (int64_t)nc <= soa.block_size[i]) {
-        for (int c = 0; c < nc; c++) {
-          uint32_t op = (uint32_t)ld32(U, cp + 4 * c);
-          uint32_t o = op & 0xf;
-          if (o == 0 || o == 2 || o == 3 || o == 7 || o == 8) rl += (int32_t)(op >> 4);
-        }
-      }
-      aend = astart + rl - 1;
+      aend = astart + cigar_ref_len(U, rec_lin[i], soa, i) - 1;
     }
     int32_t lo = ref_iv_begin[ref], hi = ref_iv_begin[ref + 1];
     // last interval with start <= aend (intervals on one reference are sorted and disjoint)
@@ -1636,6 +1643,212 @@ __global__ __launch_bounds__(256) void interval_filter_kernel(
     }
   }
   keep[t] = k;
+}
+
+// ------------------------------------------------------------------ .bai index build
+// BAMIndexer / BinningIndexBuilder over the resident records (dq_write_bai).
+// Keys: one thread per record.  key = ref << 16 | reg2bin(beg, end) (BAI_UNPLACED for a record
+// without coordinates), end = the exclusive alignment end.  The first record that breaks a rule
+// goes into *status by atomic min (index << 8 | BAI_ST_*).  Per reference, wave-reduced before the
+// atomics: meta[5 ref + 0..4] = ~(first record), last record + 1, mapped, unmapped, last linear
+// window + 1.  *no_coor counts the unplaced records.
+__device__ inline int32_t bai_reg2bin(int32_t beg, int32_t end) {  // SAMv1 §5.3
+  --end;
+  if (beg >> 14 == end >> 14) return 4681 + (beg >> 14);
+  if (beg >> 17 == end >> 17) return 585 + (beg >> 17);
+  if (beg >> 20 == end >> 20) return 73 + (beg >> 20);
+  if (beg >> 23 == end >> 23) return 9 + (beg >> 23);
+  if (beg >> 26 == end >> 26) return 1 + (beg >> 26);
+  return 0;
+}
+__device__ inline int bai_level(uint64_t key) {
+  const uint32_t b = (uint32_t)(key & 0xffff);
+  return b >= 4681 ? 5 : b >= 585 ? 4 : b >= 73 ? 3 : b >= 9 ? 2 : b >= 1 ? 1 : 0;
+}
+// the virtual offset after record i: the next record's, or the file's final pointer
+__device__ inline uint64_t bai_vend(const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
+                                    int64_t i) {
+  return i + 1 < n ? voff[i + 1] : fin;
+}
+
+__global__ __launch_bounds__(256) void bai_keys_kernel(
+    const uint8_t* __restrict__ U, const int64_t* __restrict__ rec_lin, RecSoA soa, int64_t n,
+    int32_t n_ref, uint64_t* __restrict__ key, int32_t* __restrict__ endp,
+    unsigned long long* __restrict__ meta, unsigned long long* __restrict__ status,
+    unsigned long long* __restrict__ no_coor) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool act = i < n;
+  int32_t ref = -1, pos = -1, we = -1;
+  bool placed = false, mapped = false;
+  if (act) {
+    ref = soa.ref_id[i];
+    pos = soa.pos[i];
+    placed = ref >= 0 && pos >= 0;
+    uint64_t k = BAI_UNPLACED;
+    int32_t e = 0;
+    if (placed) {
+      unsigned long long bad = 0;
+      if (i > 0) {  // sorted against record i - 1 (the placed records are then a sorted prefix)
+        const int32_t pr = soa.ref_id[i - 1], pp = soa.pos[i - 1];
+        if (pr < 0 || pp < 0 || pr > ref || (pr == ref && pp > pos)) bad = BAI_ST_UNSORTED;
+      }
+      mapped = !(soa.flag[i] & 4);
+      int64_t end = (int64_t)pos + 1;
+      if (mapped) {
+        const int32_t rl = cigar_ref_len(U, rec_lin[i], soa, i);
+        if (rl > 0) end = (int64_t)pos + rl;
+      }
+      const bool oob = ref >= n_ref || end > (1ll << 29);
+      if (!bad && oob) bad = ref >= n_ref ? BAI_ST_REF : BAI_ST_END;
+      if (bad) atomicMin(status, (unsigned long long)i << 8 | bad);
+      if (oob) placed = false;  // keep it out of the per-reference tables
+      if (placed) {
+        e = (int32_t)end;
+        k = (uint64_t)ref << 16 | (uint64_t)bai_reg2bin(pos, e);
+        we = (e - 1) >> 14;
+      }
+    }
+    key[i] = k;
+    endp[i] = e;
+  }
+  const uint64_t unp = __ballot(act && !(ref >= 0 && pos >= 0));
+  if (lane == 0 && unp) atomicAdd(no_coor, (unsigned long long)__popcll(unp));
+  // one lane per distinct reference of the wave issues the atomics (sorted input: mostly one)
+  uint64_t rem = __ballot(placed);
+  while (rem) {
+    const int l = __builtin_ctzll(rem);
+    const int32_t r = __shfl(ref, l);
+    const bool mine = placed && ref == r;
+    const uint64_t m = __ballot(mine), mm = __ballot(mine && mapped);
+    int32_t wmax = mine ? we : -1;
+    for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_xor(wmax, o));
+    if (lane == l) {
+      const int64_t i0 = i - lane;
+      unsigned long long* q = meta + 5 * (int64_t)r;
+      atomicMax(q + 0, ~(unsigned long long)(i0 + __builtin_ctzll(m)));
+      atomicMax(q + 1, (unsigned long long)(i0 + 63 - __builtin_clzll(m)) + 1);
+      atomicAdd(q + 2, (unsigned long long)__popcll(mm));
+      atomicAdd(q + 3, (unsigned long long)(__popcll(m) - __popcll(mm)));
+      atomicMax(q + 4, (unsigned long long)(wmax + 1));
+    }
+    rem &= ~m;
+  }
+}
+
+// Linear index: lin[win_off[ref] + w] = min voffset of the records reaching window w (tables
+// initialised to all ones).  In sorted input a record is a window's minimum only if no earlier
+// record of its reference reaches that window; the earlier lanes of the wave are ruled out by an
+// exclusive prefix max of (ref, last window), so one lane per window and wave issues the atomic.
+__global__ __launch_bounds__(256) void bai_linear_kernel(
+    const uint64_t* __restrict__ key, const int32_t* __restrict__ endp,
+    const int32_t* __restrict__ pos, const uint64_t* __restrict__ voff, int64_t n,
+    const int64_t* __restrict__ win_off, int64_t nwin, unsigned long long* __restrict__ lin) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const uint64_t k = i < n ? key[i] : BAI_UNPLACED;
+  const bool placed = k != BAI_UNPLACED;
+  const int32_t ref = placed ? (int32_t)(k >> 16) : -1;
+  const int32_t wb = placed ? pos[i] >> 14 : 0, we = placed ? (endp[i] - 1) >> 14 : -1;
+  int64_t m = placed ? ((int64_t)ref << 32 | (int64_t)we) : -1;  // inclusive prefix max
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t v = (int64_t)__shfl_up((long long)m, o);
+    if (lane >= o && v > m) m = v;
+  }
+  int64_t prev = (int64_t)__shfl_up((long long)m, 1);
+  if (lane == 0) prev = -1;
+  if (!placed) return;
+  const int32_t seen = prev >= 0 && (int32_t)(prev >> 32) == ref ? (int32_t)(prev & 0xffffffff) : -1;
+  const int64_t base = win_off[ref];
+  const unsigned long long vs = voff[i];
+  for (int32_t w = max(wb, seen + 1); w <= we; w++) {
+    DQ_CHK(base + w < nwin && base + w < win_off[ref + 1], CHK_BAI);
+    atomicMin(lin + base + w, vs);
+  }
+}
+
+// Pseudo-bin 37450, first chunk: span[2 r], [2 r + 1] = the start of reference r's first record
+// and the end of its last (0, 0 for a reference without records).
+__global__ __launch_bounds__(256) void bai_refspan_kernel(const unsigned long long* __restrict__ meta,
+                                                          int32_t n_ref,
+                                                          const uint64_t* __restrict__ voff,
+                                                          int64_t n, uint64_t fin,
+                                                          uint64_t* __restrict__ span) {
+  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_ref) return;
+  const unsigned long long last1 = meta[5 * (int64_t)r + 1];
+  const int64_t first = (int64_t)~meta[5 * (int64_t)r];
+  DQ_CHK(last1 == 0 || (first >= 0 && first < (int64_t)last1 && (int64_t)last1 <= n), CHK_BAI);
+  span[2 * r] = last1 ? voff[first] : 0;
+  span[2 * r + 1] = last1 ? bai_vend(voff, n, fin, (int64_t)last1 - 1) : 0;
+}
+
+// Stable partition by bin level, two levels per pass: flags for the packed scan, then the scatter
+// of the record indices into perm (level la from base_a, level la + 1 from base_b).
+__global__ __launch_bounds__(256) void bai_level_flags_kernel(const uint64_t* __restrict__ key,
+                                                              int64_t n, int la,
+                                                              int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = key[i];
+  const int l = k == BAI_UNPLACED ? -1 : bai_level(k);
+  out[i] = l == la ? 1 : l == la + 1 ? (int64_t)1 << 32 : 0;
+}
+__global__ __launch_bounds__(256) void bai_level_scatter_kernel(
+    const uint64_t* __restrict__ key, int64_t n, int la, const int64_t* __restrict__ scan,
+    int64_t base_a, int64_t base_b, int64_t nplaced, int64_t* __restrict__ perm) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = key[i];
+  if (k == BAI_UNPLACED) return;
+  const int l = bai_level(k);
+  if (l != la && l != la + 1) return;
+  const int64_t s = scan[i];
+  const int64_t j = l == la ? base_a + (s & 0xffffffff) : base_b + (s >> 32);
+  DQ_CHK(j >= 0 && j < nplaced, CHK_BAI);
+  perm[j] = i;
+}
+
+// Heads over the level-ordered records: bit 32 = the record opens a (ref, bin), bit 0 = it opens
+// a chunk (a new bin, or the bin's last chunk does not end in the record's block or the one
+// before it).
+__device__ inline int64_t bai_head(const uint64_t* __restrict__ key,
+                                   const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
+                                   const int64_t* __restrict__ perm, int64_t j) {
+  const int64_t i = perm[j];
+  if (j == 0) return ((int64_t)1 << 32) | 1;
+  const int64_t p = perm[j - 1];
+  if (key[p] != key[i]) return ((int64_t)1 << 32) | 1;
+  const uint64_t le = bai_vend(voff, n, fin, p) >> 16, vb = voff[i] >> 16;
+  return le == vb || le + 1 == vb ? 0 : 1;
+}
+__global__ __launch_bounds__(256) void bai_heads_kernel(const uint64_t* __restrict__ key,
+                                                        const uint64_t* __restrict__ voff,
+                                                        int64_t n, uint64_t fin,
+                                                        const int64_t* __restrict__ perm,
+                                                        int64_t nplaced, int64_t* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < nplaced) out[j] = bai_head(key, voff, n, fin, perm, j);
+}
+// Emit: chunk c = (voffset of its head, end of the last record of its run); bins[2 b] = key,
+// bins[2 b + 1] = the bin's first chunk.  scan = exclusive scan of the heads (chunks low, bins
+// high).
+__global__ __launch_bounds__(256) void bai_emit_kernel(
+    const uint64_t* __restrict__ key, const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
+    const int64_t* __restrict__ perm, int64_t nplaced, const int64_t* __restrict__ heads,
+    const int64_t* __restrict__ scan, int64_t nchunk, int64_t nbin, uint64_t* __restrict__ chunks,
+    uint64_t* __restrict__ bins) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nplaced) return;
+  const int64_t i = perm[j], h = heads[j], s = scan[j];
+  const int64_t c = (s & 0xffffffff) + (h & 1) - 1, b = (s >> 32) + (h >> 32) - 1;
+  DQ_CHK(c >= 0 && c < nchunk && b >= 0 && b < nbin, CHK_BAI);
+  if (h & 1) chunks[2 * c] = voff[i];
+  if (j + 1 == nplaced || (heads[j + 1] & 1)) chunks[2 * c + 1] = bai_vend(voff, n, fin, i);
+  if (h >> 32) {
+    bins[2 * b] = key[i];
+    bins[2 * b + 1] = (uint64_t)c;
+  }
 }
 
 // ------------------------------------------------------------------ windowed record chains
@@ -2194,6 +2407,60 @@ void launch_sbi_sample(const uint64_t* voffset, int64_t nrec, int64_t g, uint64_
   if (n <= 0) return;
   hipLaunchKernelGGL(sbi_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, voffset,
                      nrec, g, out);
+}
+
+static inline dim3 bai_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+void launch_bai_keys(const uint8_t* U, const int64_t* rec_lin, const RecSoA soa, int64_t n,
+                     int32_t n_ref, uint64_t* key, int32_t* endp, unsigned long long* meta,
+                     unsigned long long* status, unsigned long long* no_coor, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(bai_keys_kernel, bai_grid(n), dim3(256), 0, s, U, rec_lin, soa, n, n_ref, key,
+                     endp, meta, status, no_coor);
+}
+
+void launch_bai_linear(const uint64_t* key, const int32_t* endp, const int32_t* pos,
+                       const uint64_t* voff, int64_t n, const int64_t* win_off, int64_t nwin,
+                       unsigned long long* lin, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(bai_linear_kernel, bai_grid(n), dim3(256), 0, s, key, endp, pos, voff, n,
+                     win_off, nwin, lin);
+}
+
+void launch_bai_refspan(const unsigned long long* meta, int32_t n_ref, const uint64_t* voff,
+                        int64_t n, uint64_t fin, uint64_t* span, hipStream_t s) {
+  if (n_ref <= 0) return;
+  hipLaunchKernelGGL(bai_refspan_kernel, bai_grid(n_ref), dim3(256), 0, s, meta, n_ref, voff, n,
+                     fin, span);
+}
+
+void launch_bai_level_flags(const uint64_t* key, int64_t n, int la, int64_t* out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(bai_level_flags_kernel, bai_grid(n), dim3(256), 0, s, key, n, la, out);
+}
+
+void launch_bai_level_scatter(const uint64_t* key, int64_t n, int la, const int64_t* scan,
+                              int64_t base_a, int64_t base_b, int64_t nplaced, int64_t* perm,
+                              hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(bai_level_scatter_kernel, bai_grid(n), dim3(256), 0, s, key, n, la, scan,
+                     base_a, base_b, nplaced, perm);
+}
+
+void launch_bai_heads(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
+                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s) {
+  if (nplaced <= 0) return;
+  hipLaunchKernelGGL(bai_heads_kernel, bai_grid(nplaced), dim3(256), 0, s, key, voff, n, fin, perm,
+                     nplaced, out);
+}
+
+void launch_bai_emit(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
+                     const int64_t* perm, int64_t nplaced, const int64_t* heads,
+                     const int64_t* scan, int64_t nchunk, int64_t nbin, uint64_t* chunks,
+                     uint64_t* bins, hipStream_t s) {
+  if (nplaced <= 0) return;
+  hipLaunchKernelGGL(bai_emit_kernel, bai_grid(nplaced), dim3(256), 0, s, key, voff, n, fin, perm,
+                     nplaced, heads, scan, nchunk, nbin, chunks, bins);
 }
 
 void launch_ranges_to_idx(const int64_t* begin, const int64_t* out_off, int64_t nranges,

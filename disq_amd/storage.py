@@ -254,14 +254,20 @@ class HtsjdkReadsRddStorage:
                     parts.append(ReadsPartition(fields, raw, int(b["part_digest"][p]), f))
         return HtsjdkReadsRdd(header, ReadsRDD(parts))
 
-    def write(self, rdd: HtsjdkReadsRdd, path: str, tempPartsDirectory: Optional[str] = None):
+    def write(self, rdd: HtsjdkReadsRdd, path: str, tempPartsDirectory: Optional[str] = None, *,
+              bai: bool = False, sbi: bool = False, sbiGranularity: int = 4096):
         """BamSink.save (D/impl/formats/bam/BamSink.java:32-69) with GPU BGZF compression: each
         partition's records as a headerless BGZF part (HeaderlessBamOutputFormat, no terminator),
         the header as its own BGZF blocks, the 28-byte EOF block, then the parts merged in
         partition order (Merger.mergeParts) into `path`; the temporary parts directory is deleted
         after the merge (BamSink.java:67-68).  The header bytes are the ones the file was read
         with (header.raw), not re-encoded from a SAMFileHeader as BAMFileWriter.writeHeader does:
-        for a header read by this package they are the same BAM header."""
+        for a header read by this package they are the same BAM header.
+
+        bai / sbi: after the merge the written file is opened on the device and indexed into
+        `path + ".bai"` (dq_write_bai; the reads must be coordinate sorted) and / or
+        `path + ".sbi"` (dq_write_sbi at sbiGranularity).  They stand in for the BaiWriteOption /
+        SbiWriteOption of later Disq versions; with the defaults nothing but `path` is written."""
         header = rdd.getHeader()
         if not header.raw:
             raise ValueError("header has no BAM encoding")
@@ -284,6 +290,15 @@ class HtsjdkReadsRddStorage:
         if tempPartsDirectory:  # fileSystemWrapper.delete(tempPartsDirectory)
             import shutil
             shutil.rmtree(tempPartsDirectory, ignore_errors=True)
+        if bai or sbi:
+            with _lib.Context(device=self._device) as ctx:
+                ctx.open_path(path)
+                if bai:
+                    with open(path + ".bai", "wb") as fh:
+                        fh.write(ctx.write_bai())
+                if sbi:
+                    with open(path + ".sbi", "wb") as fh:
+                        fh.write(ctx.write_sbi(sbiGranularity))
         return path
 
     @staticmethod
@@ -431,3 +446,19 @@ class BAMSBIIndexer:
         with open(out, "wb") as fh:
             fh.write(data)
         return out
+
+
+class BAMIndexer:
+    """htsjdk BAMIndexer.createIndex on the GPU read path (dq_write_bai): the .bai of a
+    coordinate-sorted BAM, built from the resident records."""
+
+    @staticmethod
+    def createIndex(bamFile: str, output: Optional[str] = None, device: int = 0) -> str:
+        if output is None:  # the sibling AbstractSamSource.findIndex looks for (_find_index)
+            output = (bamFile[: -len(".bam")] if bamFile.endswith(".bam") else bamFile) + ".bai"
+        with _lib.Context(device=device) as ctx:
+            ctx.open_path(bamFile)
+            data = ctx.write_bai()
+        with open(output, "wb") as fh:
+            fh.write(data)
+        return output

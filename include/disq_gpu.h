@@ -22,6 +22,8 @@
  *   AbstractBinarySamSource.getReads, whole RDD (AbstractBinarySamSource.java:42-136)  dq_read
  *   AbstractSamSource.getFileHeader (D/impl/formats/sam/AbstractSamSource.java:32-49)
  *                                                                           dq_read_header
+ *   htsjdk BAMIndexer.createIndex / BinningIndexBuilder (the .bai that
+ *     AbstractBinarySamSource.java:87-91 requires for an interval traversal)    dq_write_bai
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -263,6 +265,13 @@ int dq_set_splitting_index(dq_ctx* ctx, const uint8_t* sbi, int64_t len, int32_t
  * offset from the first record, then the final pointer; zero MD5 and UUID.  *out is
  * library-allocated (dq_free); granularity <= 0 means htsjdk's default 4096. */
 int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_len);
+
+/* BAMIndexer.createIndex for the open (whole) file: the .bai file's bytes (SAMv1 §5.2; the rules
+ * are in DESIGN.md "Building the .bai").  A file that is not coordinate sorted, a reference index
+ * beyond the header's or an alignment end beyond 2^29 gives DQ_EFORMAT; a shard gives DQ_EINVAL.
+ * *out is library-allocated (dq_free); *ms (may be NULL) = device time of the index build
+ * alone, after the record pipeline. */
+int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms);
 
 /* getPathChunks: all splits of the open file, in Disq partition order.  *chunks is
  * library-allocated; free with dq_free. */

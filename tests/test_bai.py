@@ -1,0 +1,368 @@
+"""The .bai index build (dq_write_bai), DESIGN.md "Building the .bai".
+
+htsjdk is not vendored and the reference ships no .bai fixture, so the index rules (htsjdk
+BAMIndexer / BinningIndexBuilder) are pinned by the plain-Python restatement tests/baiutil.py:
+* CPU: the restatement against the oracle and the generator's own index (same traversal results,
+  same structure) and on the two reference BAMs against brute force;
+* GPU: dq_write_bai reproduces the restatement's bytes, and interval traversals through the
+  GPU-built index equal the oracle's with the generator's index.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import baiutil
+import bamutil
+from disq_amd import _lib, synth
+from disq_amd import parallel as P
+from oracle import oracle as O
+
+# tests/test_gpu_parity.py test_interval_traversal: (intervals, unplaced, expected)
+ANYSAM_CASES = [
+    ([("chr21", 5000, 9999), ("chr21", 20000, 22999)], False, 16),
+    ([("chr21", 1, 1000135)], False, 2000),
+    ([("chr21", 5000, 9999), ("chr21", 20000, 22999)], True, 18),
+    (None, True, 2),
+    ([], True, 2),
+]
+SPLITS = (40000, 8000)
+
+
+@pytest.fixture(scope="module")
+def anysam():
+    return synth.generate(1000, shape=synth.ANYSAM, bai=True)
+
+
+@pytest.fixture(scope="module")
+def wgs():
+    return synth.generate(20000, seed=3, bai=True, records_per_chunk=3000)
+
+
+@pytest.fixture(scope="module")
+def bam1(golden):
+    return open(os.path.join(golden, "1.bam"), "rb").read()
+
+
+@pytest.fixture(scope="module")
+def hiseq(golden):
+    return open(os.path.join(golden, "hiseq_part-r-00000.bam"), "rb").read()
+
+
+@pytest.fixture(scope="module")
+def multiref(bam1):
+    """Records on four of 1.bam's 85 references (0, 2, 3 and 7; the others stay empty), bins on
+    several levels (reads of 50 b, 20 kb and 150 kb), unmapped reads with a position, and an
+    unplaced tail.  The generator's WGS shape steps 5 b per record through GRCh38, so a file of
+    test size stays on chr1: the several-references case is built by hand here."""
+    mk, recs, k = bamutil.make_record, [], 0
+    for ref, n in ((0, 700), (2, 5), (3, 900), (7, 300)):
+        for i in range(n):
+            l_seq = 150000 if k % 500 == 250 else 20000 if k % 100 == 50 else 50
+            recs.append(mk(ref, 1000 + 37 * i, b"r%d" % k, l_seq, flag=4 if k % 97 == 0 else 0))
+            k += 1
+    recs += [mk(-1, -1, b"u%d" % i, 50, flag=4) for i in range(3)]
+    return _bam_of(bam1, recs)
+
+
+def _bam_of(bam1, recs):
+    u = bamutil.inflate_all(bam1)
+    return bamutil.bgzf(u[:bamutil.header_len(u)] + b"".join(recs), 5)
+
+
+@pytest.fixture(scope="module")
+def restated(anysam, wgs, bam1, hiseq, multiref):
+    """The restated index of every shared input, computed once."""
+    return {"anysam": baiutil.build_bai(anysam.bam), "wgs": baiutil.build_bai(wgs.bam),
+            "1.bam": baiutil.build_bai(bam1), "hiseq": baiutil.build_bai(hiseq),
+            "multiref": baiutil.build_bai(multiref)}
+
+
+def _conv(data, ivs):
+    ob = O.OracleBam(data)
+    return None if ivs is None else [(ob.ref_index(c), s, e) for c, s, e in ivs]
+
+
+def _wgs_intervals(data):
+    """Three seeded intervals on every reference of the file: inside the range its records cover,
+    or inside its length when it has none."""
+    ob = O.OracleBam(data)
+    lens, recs = ob.header()["ref_lengths"], ob.read_all()
+    rng = np.random.default_rng(7)
+    ivs = []
+    for r, ln in enumerate(lens):
+        pos = recs["pos"][(recs["ref_id"] == r) & (recs["pos"] >= 0)]
+        lo, hi = (int(pos.min()) + 1, int(pos.max()) + 2) if len(pos) else (1, max(2, int(ln)))
+        for s in rng.integers(lo, hi, size=3):
+            ivs.append((r, int(s), int(s + rng.integers(10, 3000))))
+    return ivs
+
+
+def _brute(data, ivs):
+    """voffsets of the records overlapping ivs, by O.overlaps over every record."""
+    q = O.optimize_intervals(ivs)
+    recs = O.OracleBam(data).read_all()
+    return np.array([int(r["voffset"]) for r in recs if O.overlaps(r, q)], np.uint64)
+
+
+def _two_intervals(data):
+    """Two intervals around the quartile records of the file's placed records."""
+    recs = O.OracleBam(data).read_all()
+    placed = recs[(recs["ref_id"] >= 0) & (recs["pos"] >= 0)]
+    a, b = placed[len(placed) // 4], placed[3 * len(placed) // 4]
+    return [(int(a["ref_id"]), int(a["pos"]) + 1, int(a["pos"]) + 2000),
+            (int(b["ref_id"]), max(1, int(b["pos"]) - 500), int(b["pos"]) + 5000)]
+
+
+# ---------------------------------------------------------------------------- CPU: the contract
+def test_restatement_oracle_agreement_anysam(anysam, restated):
+    mine = restated["anysam"]
+    assert O.bai_info(mine) == O.bai_info(anysam.bai)
+    for split in SPLITS:
+        splits = O.path_splits(len(anysam.bam), split)
+        for ivs, unplaced, expected in ANYSAM_CASES:
+            conv = _conv(anysam.bam, ivs)
+            for spans in (True, False):
+                want = O.run_partitions_traversal(anysam.bam, splits, 2, anysam.bai, conv, unplaced, spans)
+                got = O.run_partitions_traversal(anysam.bam, splits, 2, mine, conv, unplaced, spans)
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+            # Disq's split-boundary duplicates aside (BamSource.java:140), the expected count
+            one = O.run_partitions_traversal(anysam.bam, O.path_splits(len(anysam.bam), 0), 1, mine,
+                                             conv, unplaced, True)
+            assert int(one[0].sum()) == expected
+
+
+def test_restatement_oracle_agreement_wgs(wgs, restated):
+    mine = restated["wgs"]
+    assert O.bai_info(mine) == O.bai_info(wgs.bai)
+    ivs = _wgs_intervals(wgs.bam)
+    for split in SPLITS:
+        splits = O.path_splits(len(wgs.bam), split)
+        for spans in (True, False):
+            want = O.run_partitions_traversal(wgs.bam, splits, 4, wgs.bai, ivs, False, spans)
+            got = O.run_partitions_traversal(wgs.bam, splits, 4, mine, ivs, False, spans)
+            assert want[0].sum() > 0
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+@pytest.mark.parametrize("name", ["anysam", "wgs"])
+def test_restatement_structure_equals_generator(name, anysam, wgs, restated):
+    gen_refs, gen_nc = baiutil.parse_bai({"anysam": anysam, "wgs": wgs}[name].bai)
+    refs, nc = baiutil.parse_bai(restated[name])
+    assert nc == gen_nc and len(refs) == len(gen_refs)
+    for g, r in zip(gen_refs, refs):
+        assert set(g["bins"]) == set(r["bins"])
+        assert g["meta"] == r["meta"]
+        assert len(g["linear"]) == len(r["linear"])
+        for b, chunks in g["bins"].items():   # the restated chunks merge more, never cover less
+            for lo, hi in chunks:
+                assert any(a <= lo and hi <= e for a, e in r["bins"][b]), (b, lo, hi)
+
+
+def baiutil_level(b):
+    return sum(b >= first for first in (1, 9, 73, 585, 4681))
+
+
+def test_restatement_multiref(multiref, restated):
+    """References with and without records, bins on several levels, several chunks per bin: the
+    traversal through the restated index selects what brute force selects."""
+    refs, nc = baiutil.parse_bai(restated["multiref"])
+    with_recs = [i for i, r in enumerate(refs) if r["meta"] is not None]
+    assert with_recs == [0, 2, 3, 7] and len(refs) == 85 and nc == 3
+    assert all(not refs[i]["bins"] and not refs[i]["linear"] for i in (1, 4, 5, 6, 8, 84))
+    assert len({baiutil_level(b) for r in refs for b in r["bins"]}) >= 3
+    assert any(len(ch) > 1 for r in refs for ch in r["bins"].values())
+    assert sum(r["meta"][1][1] for r in refs if r["meta"]) > 0      # unmapped with a position
+    ivs = [(0, 1500, 1600), (2, 1, 0), (3, 30000, 30100), (5, 1, 1000), (7, 1, 1100)]
+    want = _brute(multiref, ivs)
+    assert len(want) > 10
+    for spans in (True, False):
+        parts = O.OracleBam(multiref).read_partitions(0, traversal=(ivs, True), bai=restated["multiref"],
+                                                      spans=spans)
+        got = np.concatenate([p["voffset"] for p in parts])
+        assert np.array_equal(got[:-3], want) and len(got) == len(want) + 3   # + the unplaced tail
+
+
+def test_restatement_golden_1bam(bam1, restated):
+    n_ref, recs = baiutil.records(bam1)
+    assert len(recs) == 4917 and n_ref == 85
+    assert sum(1 for r in recs if r[4] & 4 and r[2] >= 0 and r[3] >= 0) == 30
+    refs, nc = baiutil.parse_bai(restated["1.bam"])
+    assert nc == 0 and [i for i, r in enumerate(refs) if r["meta"] is not None] == [0]
+    assert len(refs[0]["bins"]) == 6
+    assert len(refs[0]["linear"]) == 1525          # windows up to 1524
+    assert refs[0]["meta"][1] == (4917 - 30, 30)
+    # every record's stored bin field is the computed one (htsjdk trusts the field)
+    allr = O.OracleBam(bam1).read_all()
+    for r, (vs, ve, ref_id, pos, flag, rl) in zip(allr, recs):
+        end = pos + rl if not flag & 4 and rl > 0 else pos + 1
+        assert int(r["bin"]) == baiutil.reg2bin(pos, end) and int(r["voffset"]) == vs
+
+
+def test_restatement_golden_hiseq(hiseq, restated):
+    n_ref, recs = baiutil.records(hiseq)
+    refs, nc = baiutil.parse_bai(restated["hiseq"])
+    assert nc == 12 and len(refs) == n_ref
+    assert hiseq[-28:] != bamutil.EOF_BLOCK         # no EOF block: the last end is the file's
+    assert recs[-1][1] == len(hiseq) << 16
+    allr = O.OracleBam(hiseq).read_all()
+    for r, (vs, ve, ref_id, pos, flag, rl) in zip(allr, recs):
+        if ref_id >= 0 and pos >= 0:
+            end = pos + rl if not flag & 4 and rl > 0 else pos + 1
+            assert int(r["bin"]) == baiutil.reg2bin(pos, end)
+
+
+@pytest.mark.parametrize("name", ["1.bam", "hiseq"])
+def test_restatement_golden_traversal_equals_brute_force(name, bam1, hiseq, restated):
+    data = {"1.bam": bam1, "hiseq": hiseq}[name]
+    ivs = _two_intervals(data)
+    want = _brute(data, ivs)
+    assert len(want) > 0
+    parts = O.OracleBam(data).read_partitions(0, traversal=(ivs, False), bai=restated[name],
+                                              spans=True)
+    assert np.array_equal(np.concatenate([p["voffset"] for p in parts]), want)
+
+
+# ---------------------------------------------------------------------------- GPU
+def _ctx(data, split=0, **kw):
+    c = _lib.Context(split_size=split, verify_crc=True, **kw)
+    c.open_bytes(data)
+    return c
+
+
+def _header_only(anysam):
+    u = bamutil.inflate_all(anysam.bam)
+    return bamutil.bgzf(u[:bamutil.header_len(u)], 5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["1.bam", "hiseq", "anysam", "wgs", "multiref", "longread",
+                                  "header_only"])
+def test_gpu_bai_equals_restatement(name, bam1, hiseq, anysam, wgs, multiref, restated):
+    if name == "longread":   # records over many windows and BGZF blocks, high-level bins
+        data = synth.generate(60, seed=5, shape=synth.LONGREAD).bam
+        want = baiutil.build_bai(data)
+        refs, _ = baiutil.parse_bai(want)
+        assert min(baiutil_level(b) for r in refs for b in r["bins"]) <= 3   # 1 Mb bins or wider
+    elif name == "header_only":
+        data = _header_only(anysam)
+        want = baiutil.build_bai(data)
+        refs, nc = baiutil.parse_bai(want)
+        assert nc == 0 and all(not r["bins"] and not r["linear"] and r["meta"] is None for r in refs)
+    else:
+        data = {"1.bam": bam1, "hiseq": hiseq, "anysam": anysam.bam, "wgs": wgs.bam,
+                "multiref": multiref}[name]
+        want = restated[name]
+    n = len(baiutil.records(data)[1])
+    with _ctx(data) as c:
+        got = c.write_bai()
+        assert got == want
+        assert c.write_bai() == got                 # a second call on the context: same bytes
+        assert c.bai_ms >= 0
+        assert len(c.read(with_raw=False)["voffset"]) == n   # the context reads normally afterwards
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("split", [40000, 8000, 3000])
+def test_gpu_bai_end_to_end_anysam(anysam, split):
+    splits = O.path_splits(len(anysam.bam), split)
+    with _ctx(anysam.bam, split) as c:
+        c.set_index(c.write_bai())
+        for ivs, unplaced, expected in ANYSAM_CASES:
+            conv = _conv(anysam.bam, ivs)
+            b = c.read(with_raw=False, traversal=(conv, unplaced))
+            cnt, dig = O.run_partitions_traversal(anysam.bam, splits, 2, anysam.bai, conv, unplaced,
+                                                  True)
+            po = b["part_offset"]
+            live = [i for i, (_, _, ch) in enumerate(O.OracleBam(anysam.bam).plan(split))
+                    if ch is not None]
+            assert len(po) - 1 == len(live)
+            assert np.array_equal(np.diff(po), cnt[live])
+            assert np.array_equal(np.asarray(b["part_digest"], np.uint64), dig[live])
+    with _ctx(anysam.bam, 0) as c:   # one partition: the counts of test_interval_traversal
+        c.set_index(c.write_bai())
+        for ivs, unplaced, expected in ANYSAM_CASES:
+            b = c.read(with_raw=False, traversal=(_conv(anysam.bam, ivs), unplaced))
+            assert len(b["voffset"]) == expected
+        st = c.run_resident((_conv(anysam.bam, ANYSAM_CASES[0][0]), False))
+        assert st.n_filtered == 16 and 0 < st.blocks_inflated <= st.n_blocks
+
+
+@pytest.mark.gpu
+def test_gpu_bai_end_to_end_1bam(bam1):
+    """1.bam's first interval read: through the GPU-built index, against brute force."""
+    ivs = _two_intervals(bam1)
+    want = _brute(bam1, ivs)
+    with _ctx(bam1) as c:
+        c.set_index(c.write_bai())
+        b = c.read(with_raw=False, traversal=(ivs, False))
+        assert np.array_equal(b["voffset"], want)
+        st = c.run_resident((ivs, False))
+        assert st.n_filtered == len(want) and 0 < st.blocks_inflated <= st.n_blocks
+
+
+@pytest.mark.gpu
+def test_gpu_bai_errors(bam1, anysam):
+    mk = bamutil.make_record
+    unsorted = _bam_of(bam1, [mk(0, 100, b"a", 50), mk(0, 200, b"b", 50), mk(0, 150, b"c", 50),
+                              mk(0, 120, b"d", 50)])
+    after_unplaced = _bam_of(bam1, [mk(0, 100, b"a", 50), mk(-1, -1, b"b", 50, flag=4),
+                                    mk(0, 300, b"c", 50)])
+    with pytest.raises(ValueError, match="not coordinate sorted: record 2 "):
+        baiutil.build_bai(unsorted)
+    with pytest.raises(ValueError, match="not coordinate sorted"):
+        baiutil.build_bai(after_unplaced)
+    for data, pat, n in ((unsorted, "not coordinate sorted: record 2 ", 4),
+                         (after_unplaced, "not coordinate sorted", 3)):
+        with _ctx(data) as c:
+            with pytest.raises(_lib.DqError, match=pat) as e:
+                c.write_bai()
+            assert e.value.code == _lib.DQ_EFORMAT
+            assert len(c.read(with_raw=False)["voffset"]) == n   # still usable
+    data, split = anysam.bam, 40000
+    with _lib.Context(split_size=split) as c:
+        hdr = c.header_from_prefix(data[:1 << 20])
+    s = P.shard_plan(len(data), 1, split_size=split)[0]
+    with _lib.Context(split_size=split) as c:
+        c.open_shard(data[s.lo:], s.lo, len(data), s.p0, s.p1, hdr)
+        with pytest.raises(_lib.DqError, match="indexes a whole file, not a shard") as e:
+            c.write_bai()
+        assert e.value.code == _lib.DQ_EINVAL
+        assert len(c.read(with_raw=False)["voffset"]) > 0
+
+
+@pytest.mark.gpu
+def test_gpu_bai_storage(tmp_path, bam1, anysam):
+    from disq_amd.storage import (BAMIndexer, BAMSBIIndexer, HtsjdkReadsRddStorage,
+                                  HtsjdkReadsTraversalParameters, Interval)
+    p = str(tmp_path / "1.bam")
+    with open(p, "wb") as fh:
+        fh.write(bam1)
+    ivs = _two_intervals(bam1)
+    name = HtsjdkReadsRddStorage.makeDefault().read(p).getHeader().getSequenceDictionary()[0][0]
+    tp = HtsjdkReadsTraversalParameters([Interval(name, s, e) for _, s, e in ivs], False)
+    st = HtsjdkReadsRddStorage.makeDefault()
+    with pytest.raises(ValueError, match="no index file found"):
+        st.read(p, tp)
+    out = BAMIndexer.createIndex(p)
+    assert out == str(tmp_path / "1.bai") and os.path.exists(out)
+    assert st.read(p, tp).getReads().count() == len(_brute(bam1, ivs))
+    # write with both indexes, read the written file back with intervals
+    src = str(tmp_path / "anysam.bam")
+    anysam.write(src)
+    rdd = st.read(src)
+    w = str(tmp_path / "out" / "w.bam")
+    os.makedirs(os.path.dirname(w))
+    st.write(rdd, w, bai=True, sbi=True)
+    tp18 = HtsjdkReadsTraversalParameters(
+        [Interval("chr21", 5000, 9999), Interval("chr21", 20000, 22999)], True)
+    assert st.read(w, tp18).getReads().count() == 18
+    sbi = open(w + ".sbi", "rb").read()
+    os.remove(w + ".sbi")
+    assert open(BAMSBIIndexer.createIndex(w), "rb").read() == sbi
+    # the defaults: the same bytes, no sidecar files
+    d = tmp_path / "plain"
+    d.mkdir()
+    st.write(rdd, str(d / "w.bam"))
+    assert os.listdir(d) == ["w.bam"]
+    assert open(d / "w.bam", "rb").read() == open(w, "rb").read()
