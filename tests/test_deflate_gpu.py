@@ -7,7 +7,6 @@ library) to exactly the input; a BAM assembled as BamSink.save does (header bloc
 EOF block) reads back through the oracle to the same records.  Compressed bytes are not compared
 with java.util.zip.Deflater's (a different encoder): parity is on the decompressed content."""
 import os
-import struct
 import zlib
 
 import numpy as np
@@ -16,24 +15,19 @@ import pytest
 from disq_amd import _lib, synth
 from oracle import oracle as O
 import bamutil as B
+import deflate_reader
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def members(bgzf):
-    out, p = [], 0
-    while p < len(bgzf):
-        h = bgzf[p:p + 18]
-        assert h[:4] == b"\x1f\x8b\x08\x04" and h[10:12] == b"\x06\x00" and h[12:14] == b"BC"
-        cs = struct.unpack_from("<H", h, 16)[0] + 1
-        body = bgzf[p + 18:p + cs - 8]
-        crc, isize = struct.unpack_from("<II", bgzf, p + cs - 8)
+    """The decompressed members (deflate_reader.members checks the BGZF layout and BSIZE)."""
+    out = []
+    for body, crc, isize in deflate_reader.members(bytes(bgzf)):
         data = zlib.decompress(body, -15)
         assert len(data) == isize and zlib.crc32(data) & 0xffffffff == crc
         out.append(data)
-        p += cs
-    assert p == len(bgzf)
     return out
 
 
