@@ -113,7 +113,8 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_text_open_path", "dq_text_run", "dq_text_read", "dq_text_batch_free",
            "dq_bgzf_compress", "dq_bgzf_compress_resident", "dq_bgzf_fetch",
            "dq_text_set_index", "dq_text_set_intervals", "dq_decode_file_multi",
-           "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai")
+           "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai",
+           "dq_text_write_tbi")
 
 _lib = None
 _lock = threading.Lock()
@@ -183,6 +184,7 @@ def lib():
         L.dq_text_set_index.argtypes = [vp, vp, C.c_int64]
         L.dq_text_set_intervals.argtypes = [vp, P(C.c_char_p), P(C.c_int32), P(C.c_int32),
                                             C.c_int64]
+        L.dq_text_write_tbi.argtypes = [vp, P(P(C.c_uint8)), P(C.c_int64), P(C.c_double)]
         L.dq_bgzf_compress.argtypes = [vp, vp, C.c_int64, P(C.c_void_p), P(C.c_int64)]
         L.dq_bgzf_compress_resident.argtypes = [vp, P(C.c_int64), P(C.c_double)]
         L.dq_bgzf_fetch.argtypes = [vp, vp, C.c_int64]
@@ -509,6 +511,18 @@ class Context:
         finally:
             lib().dq_text_batch_free(bp)
 
+    def text_write_tbi(self) -> bytes:
+        """htsjdk TabixIndexCreator over the open text file (dq_text_write_tbi): the decompressed
+        tabix bytes, the form text_set_index takes.  The device time of the index build alone is
+        kept in `tbi_ms`."""
+        p = C.POINTER(C.c_uint8)()
+        n, ms = C.c_int64(), C.c_double()
+        check(self._h, lib().dq_text_write_tbi(self._h, C.byref(p), C.byref(n), C.byref(ms)))
+        out = _copy_out(C.cast(p, C.c_void_p).value, n.value)
+        lib().dq_free(C.cast(p, C.c_void_p))
+        self.tbi_ms = ms.value
+        return out
+
     def set_index(self, bai_bytes):
         if bai_bytes is None:
             check(self._h, lib().dq_set_index(self._h, None, 0))
@@ -645,7 +659,7 @@ CHECK_SITES = ("K1 candidate slot", "K2 bit reader word", "K2 image store", "K2 
                "K2 per-lane arrays", "K2 match bitmap", "K2 resolve next pointer",
                "K2 resolve source", "K3 record staging", "K2 last_start",
                "deflate bucket-list slot", "deflate staged symbol", "deflate image word",
-               "K3 segment speculation")
+               "K3 segment speculation", ".bai table slot", ".tbi table slot")
 
 
 def checked_report():

@@ -1035,6 +1035,28 @@ static int run_pipeline(dq_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ BGZF text (VCF) path
+// The terminator list of the resident stream: ctx->t_term[0, ctx->t_nterm), ascending.
+static int text_terms(dq_ctx* ctx) {
+  hipStream_t s = ctx->s;
+  const int64_t ulen = ctx->ulen;
+  int rc;
+  const int64_t nt = text_tiles(ulen);
+  if ((rc = ensure_all(ctx, ctx->t_tcount, 4 * (size_t)std::max<int64_t>(1, nt)))) return rc;
+  if ((rc = ensure_all(ctx, ctx->t_toff, 8 * (size_t)(nt + 1)))) return rc;
+  if ((rc = ensure_all(ctx, ctx->tmp, sizeof(int64_t) * (size_t)(4 * (nt / 1024 + 1) + 4096)))) return rc;
+  launch_text_terms(ctx->U.as<uint8_t>(), ulen, ctx->t_tcount.as<int32_t>(), nullptr, nullptr, false, s);
+  if (nt > 0)
+    launch_exclusive_scan_i32(ctx->t_tcount.as<int32_t>(), ctx->t_toff.as<int64_t>(), nt,
+                              ctx->tmp.as<int64_t>(), s);
+  int64_t nterm = 0;
+  if (nt > 0 && (rc = get_i64(ctx, ctx->t_toff.as<int64_t>() + nt, &nterm))) return rc;
+  if ((rc = ensure_all(ctx, ctx->t_term, 8 * (size_t)(nterm + 1)))) return rc;
+  launch_text_terms(ctx->U.as<uint8_t>(), ulen, nullptr, ctx->t_toff.as<int64_t>(),
+                    ctx->t_term.as<int64_t>(), true, s);
+  ctx->t_nterm = nterm;
+  return 0;
+}
+
 // TextInputFormat + LineRecordReader over Disq's splittable BGZF codec, per split (dq_text.hip
 // holds the characterisation, oracle/disq_oracle.c the literal restatement): terminators of the
 // resident stream, each split's line range, the values (drop '#' lines as VcfSource does), their
@@ -1056,21 +1078,8 @@ static int text_run(dq_ctx* ctx, int32_t drop_hash) {
     for (int64_t b = 0; b + 1 < nblk; b++)
       if (us[(size_t)b] == 0) RET(DQ_EFORMAT, "empty BGZF block inside a text stream is not supported");
   }
-  // terminators
-  const int64_t nt = text_tiles(ulen);
-  if ((rc = ensure_all(ctx, ctx->t_tcount, 4 * (size_t)std::max<int64_t>(1, nt)))) return rc;
-  if ((rc = ensure_all(ctx, ctx->t_toff, 8 * (size_t)(nt + 1)))) return rc;
-  if ((rc = ensure_all(ctx, ctx->tmp, sizeof(int64_t) * (size_t)(4 * (nt / 1024 + 1) + 4096)))) return rc;
-  launch_text_terms(ctx->U.as<uint8_t>(), ulen, ctx->t_tcount.as<int32_t>(), nullptr, nullptr, false, s);
-  if (nt > 0)
-    launch_exclusive_scan_i32(ctx->t_tcount.as<int32_t>(), ctx->t_toff.as<int64_t>(), nt,
-                              ctx->tmp.as<int64_t>(), s);
-  int64_t nterm = 0;
-  if (nt > 0 && (rc = get_i64(ctx, ctx->t_toff.as<int64_t>() + nt, &nterm))) return rc;
-  if ((rc = ensure_all(ctx, ctx->t_term, 8 * (size_t)(nterm + 1)))) return rc;
-  launch_text_terms(ctx->U.as<uint8_t>(), ulen, nullptr, ctx->t_toff.as<int64_t>(),
-                    ctx->t_term.as<int64_t>(), true, s);
-  ctx->t_nterm = nterm;
+  if ((rc = text_terms(ctx))) return rc;
+  const int64_t nterm = ctx->t_nterm;
   if ((rc = ensure_all(ctx, ctx->t_crf, 8 * (size_t)std::max<int64_t>(1, nblk)))) return rc;
   launch_text_cr_fills(ctx->U.as<uint8_t>(), ctx->uoff.as<int64_t>(), ctx->blk_us.as<int32_t>(), nblk,
                        ctx->t_crf.as<int64_t>(), s);
@@ -3397,6 +3406,239 @@ int dq_text_read(dq_ctx* ctx, int32_t drop_header_lines, dq_text_batch** out) {
   }
   b->part_offset[nsplit] = n;
   *out = b;
+  return 0;
+}
+
+// TabixIndexCreator / BinningIndexBuilder (DESIGN.md "Building the .tbi"): data lines, their keys
+// and runs on the device (dq_text.hip), then the .bai kernels over the same key / voff / endp / pos
+// arrays; the host names the contigs, orders the bin headers and serialises.
+int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
+  if (!ctx || !out || !out_len) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  if (!ctx->have_file || !ctx->text_mode) RET(DQ_EINVAL, "dq_text_write_tbi: no text file open (dq_text_open_*)");
+  if (ctx->shard) RET(DQ_EINVAL, "dq_text_write_tbi indexes a whole file, not a shard");
+  int rc = run_pipeline(ctx);
+  if (rc) return rc;
+  if ((rc = text_terms(ctx))) return rc;
+  if (ms) *ms = 0;
+  hipStream_t s = ctx->s;
+  const int64_t nblk = ctx->nblk, ulen = ctx->ulen, nterm = ctx->t_nterm;
+  const uint8_t* U = ctx->U.as<uint8_t>();
+  const int64_t* term = ctx->t_term.as<int64_t>();
+  // lines, and the final pointer: the first block after the last non-empty one, or the file's end
+  int64_t last_term = -1;
+  if (nterm && (rc = get_i64(ctx, term + nterm - 1, &last_term))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  const int64_t nl = nterm + (last_term + 1 < ulen ? 1 : 0);
+  uint64_t fin = (uint64_t)ctx->flen << 16;
+  if (ulen > 0) {
+    std::vector<int64_t> uo((size_t)nblk), bp((size_t)nblk);
+    HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
+    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end(), ulen - 1) - uo.begin()) - 1;
+    if (j + 1 < nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
+  }
+  if (nl > INT32_MAX) RET(DQ_EINVAL, "dq_text_write_tbi: more than 2147483647 lines");
+  struct Ev {
+    hipEvent_t e = nullptr;
+    ~Ev() {
+      if (e) (void)hipEventDestroy(e);
+    }
+  } e0, e1;
+  HIPCHK(hipEventCreate(&e0.e));
+  HIPCHK(hipEventCreate(&e1.e));
+  HIPCHK(hipEventRecord(e0.e, s));
+  DevBuf d_flag, d_off, d_dl, d_pos, d_end, d_vs, d_ve, d_head, d_st, d_key, d_meta, d_nfirst,
+      d_nline, d_nstart, d_nlen, d_noff, d_names, d_woff, d_lin, d_in, d_sc, d_perm, d_chunks, d_bins;
+  // the compacted list of data lines
+  int64_t n = 0;
+  if (nl > 0) {
+    if ((rc = ensure_scan(ctx, nl))) return rc;
+    HIPCHK(d_flag.ensure(4 * (size_t)nl));
+    HIPCHK(d_off.ensure(8 * ((size_t)nl + 1)));
+    launch_tbi_lines(U, ulen, term, nterm, nl, d_flag.as<int32_t>(), s);
+    launch_exclusive_scan_i32(d_flag.as<int32_t>(), d_off.as<int64_t>(), nl, ctx->tmp.as<int64_t>(), s);
+    if ((rc = get_i64(ctx, d_off.as<int64_t>() + nl, &n))) return rc;
+  }
+  int64_t nrun = 0;
+  unsigned long long status = ~0ull;
+  if (n > 0) {
+    HIPCHK(d_dl.ensure(8 * (size_t)n));
+    HIPCHK(d_pos.ensure(4 * (size_t)n));
+    HIPCHK(d_end.ensure(4 * (size_t)n));
+    HIPCHK(d_vs.ensure(8 * (size_t)n));
+    HIPCHK(d_ve.ensure(8 * (size_t)n));
+    HIPCHK(d_head.ensure(4 * (size_t)n));
+    HIPCHK(d_sc.ensure(8 * ((size_t)n + 1)));
+    HIPCHK(d_st.ensure(8));
+    HIPCHK(hipMemsetAsync(d_st.p, 0xff, 8, s));
+    launch_tbi_compact(d_flag.as<int32_t>(), d_off.as<int64_t>(), nl, n, d_dl.as<int64_t>(), s);
+    launch_tbi_keys(U, ulen, term, nterm, d_dl.as<int64_t>(), n, ctx->uoff.as<int64_t>(),
+                    ctx->blk_pos.as<int64_t>(), nblk, fin, d_pos.as<int32_t>(), d_end.as<int32_t>(),
+                    d_vs.as<uint64_t>(), d_ve.as<uint64_t>(), d_head.as<int32_t>(),
+                    d_st.as<unsigned long long>(), s);
+    // run numbering: a scan of the run-head flags
+    launch_exclusive_scan_i32(d_head.as<int32_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
+    HIPCHK(hipMemcpyAsync(&status, d_st.p, 8, hipMemcpyDeviceToHost, s));
+    if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &nrun))) return rc;
+  }
+  // keys, the per-run table and the run heads' CHROM bytes
+  std::vector<unsigned long long> meta(5 * (size_t)nrun, 0);
+  std::vector<int64_t> nline((size_t)nrun), noff((size_t)nrun + 1, 0);
+  std::vector<int32_t> nlen((size_t)nrun);
+  std::vector<std::string> names((size_t)nrun);
+  if (nrun > 0) {
+    HIPCHK(d_key.ensure(8 * (size_t)n));
+    HIPCHK(d_meta.ensure(8 * meta.size()));
+    HIPCHK(d_nfirst.ensure(8 * (size_t)nrun));
+    HIPCHK(d_nline.ensure(8 * (size_t)nrun));
+    HIPCHK(d_nstart.ensure(8 * (size_t)nrun));
+    HIPCHK(d_nlen.ensure(4 * (size_t)nrun));
+    HIPCHK(d_noff.ensure(8 * noff.size()));
+    HIPCHK(hipMemsetAsync(d_meta.p, 0, 8 * meta.size(), s));
+    launch_tbi_runs(U, ulen, term, nterm, d_dl.as<int64_t>(), n, d_head.as<int32_t>(),
+                    d_sc.as<int64_t>(), nrun, d_pos.as<int32_t>(), d_end.as<int32_t>(),
+                    d_key.as<uint64_t>(), d_meta.as<unsigned long long>(), d_nfirst.as<int64_t>(),
+                    d_nline.as<int64_t>(),
+                    d_nstart.as<int64_t>(), d_nlen.as<int32_t>(), s);
+    HIPCHK(hipMemcpyAsync(meta.data(), d_meta.p, 8 * meta.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nline.data(), d_nline.p, 8 * (size_t)nrun, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(nlen.data(), d_nlen.p, 4 * (size_t)nrun, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // names of the runs that start before the first offender (later ones do not matter)
+    const int64_t bad_line = status == ~0ull ? INT64_MAX : (int64_t)(status >> 8);
+    for (int64_t r = 0; r < nrun; r++)
+      noff[(size_t)r + 1] = noff[(size_t)r] + (nline[(size_t)r] < bad_line ? (int64_t)nlen[(size_t)r] : 0);
+    const int64_t nbytes = noff[(size_t)nrun];
+    std::vector<char> nb((size_t)nbytes);
+    if (nbytes > 0) {
+      HIPCHK(d_names.ensure((size_t)nbytes));
+      HIPCHK(hipMemcpyAsync(d_noff.p, noff.data(), 8 * noff.size(), hipMemcpyHostToDevice, s));
+      launch_tbi_names(U, d_nstart.as<int64_t>(), d_nlen.as<int32_t>(), d_noff.as<int64_t>(), nrun,
+                       nbytes, d_names.as<uint8_t>(), s);
+      HIPCHK(hipMemcpyAsync(nb.data(), d_names.p, (size_t)nbytes, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    // a CHROM that already ended an earlier run: the later run's first line is out of order
+    std::vector<std::pair<std::string, int64_t>> byname;
+    for (int64_t r = 0; r < nrun && nline[(size_t)r] < bad_line; r++) {
+      names[(size_t)r].assign(nb.data() + noff[(size_t)r], (size_t)(noff[(size_t)r + 1] - noff[(size_t)r]));
+      byname.push_back({names[(size_t)r], r});
+    }
+    std::sort(byname.begin(), byname.end());
+    int64_t rep = INT64_MAX;
+    for (size_t i = 1; i < byname.size(); i++)
+      if (byname[i].first == byname[i - 1].first) rep = std::min(rep, nline[(size_t)byname[i].second]);
+    if (rep < bad_line) status = (unsigned long long)rep << 8 | TBI_ST_UNSORTED;
+  }
+  if (status != ~0ull) {
+    const std::string at = "line " + std::to_string((long long)(status >> 8));
+    switch ((int)(status & 0xff)) {
+      case TBI_ST_FORMAT: RET(DQ_EFORMAT, at + " is not a VCF record");
+      case TBI_ST_RANGE: RET(DQ_EFORMAT, at + ": POS below 1 or end beyond 2^29, the tabix limit");
+      default: RET(DQ_EFORMAT, "not sorted: " + at);
+    }
+  }
+  // from here on as dq_write_bai: linear index, level partition, heads, emit
+  std::vector<int64_t> woff((size_t)nrun + 1, 0);
+  for (int64_t r = 0; r < nrun; r++) woff[(size_t)r + 1] = woff[(size_t)r] + (int64_t)meta[5 * (size_t)r + 4];
+  const int64_t nwin = woff[(size_t)nrun];
+  int64_t nchunk = 0, nbin = 0;
+  std::vector<uint64_t> lin((size_t)nwin), chunks, bins;
+  if (n > 0) {
+    const uint64_t* voff = d_vs.as<uint64_t>();
+    const uint64_t* vend = d_ve.as<uint64_t>();
+    HIPCHK(d_woff.ensure(8 * woff.size()));
+    HIPCHK(d_lin.ensure(8 * (size_t)std::max<int64_t>(1, nwin)));
+    HIPCHK(hipMemcpyAsync(d_woff.p, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_lin.p, 0xff, 8 * (size_t)nwin, s));
+    launch_bai_linear(d_key.as<uint64_t>(), d_end.as<int32_t>(), d_pos.as<int32_t>(), voff, n,
+                      d_woff.as<int64_t>(), nwin, d_lin.as<unsigned long long>(), s);
+    HIPCHK(d_in.ensure(8 * (size_t)n));
+    HIPCHK(d_perm.ensure(8 * (size_t)n));
+    int64_t base = 0;
+    for (int la = 0; la < 6; la += 2) {
+      launch_bai_level_flags(d_key.as<uint64_t>(), n, la, d_in.as<int64_t>(), s);
+      launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
+      int64_t tot = 0;
+      if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
+      const int64_t a = tot & 0xffffffff, b = tot >> 32;
+      launch_bai_level_scatter(d_key.as<uint64_t>(), n, la, d_sc.as<int64_t>(), base, base + a, n,
+                               d_perm.as<int64_t>(), s);
+      base += a + b;
+    }
+    if (base != n) RET(DQ_EDEVICE, "dq_text_write_tbi: level partition lost lines");
+    launch_bai_heads(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), n, d_in.as<int64_t>(), s, vend);
+    launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
+    int64_t tot = 0;
+    if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
+    nchunk = tot & 0xffffffff;
+    nbin = tot >> 32;
+    HIPCHK(d_chunks.ensure(16 * (size_t)nchunk));
+    HIPCHK(d_bins.ensure(16 * (size_t)nbin));
+    launch_bai_emit(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), n, d_in.as<int64_t>(),
+                    d_sc.as<int64_t>(), nchunk, nbin, d_chunks.as<uint64_t>(), d_bins.as<uint64_t>(), s,
+                    vend);
+    chunks.resize(2 * (size_t)nchunk);
+    bins.resize(2 * (size_t)nbin);
+    HIPCHK(hipMemcpyAsync(chunks.data(), d_chunks.p, 8 * chunks.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(bins.data(), d_bins.p, 8 * bins.size(), hipMemcpyDeviceToHost, s));
+    if (nwin) HIPCHK(hipMemcpyAsync(lin.data(), d_lin.p, 8 * lin.size(), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipEventRecord(e1.e, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ms) *ms = ev_ms(e0.e, e1.e);
+  // htsjdk TabixIndex.write: magic, n_ref, the VCF format (flags 2, sequence column 1, begin
+  // column 2, end column 0, meta '#', skip 0), the names, then the .bai layout per contig with
+  // neither pseudo-bin nor trailing count
+  std::vector<int64_t> order((size_t)nbin);
+  for (int64_t b = 0; b < nbin; b++) order[(size_t)b] = b;
+  std::sort(order.begin(), order.end(),
+            [&](int64_t x, int64_t y) { return bins[2 * (size_t)x] < bins[2 * (size_t)y]; });
+  std::vector<uint8_t> o;
+  auto p32 = [&](uint32_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
+  auto p64 = [&](uint64_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 8); };
+  o.insert(o.end(), {'T', 'B', 'I', 1});
+  p32((uint32_t)nrun);
+  for (uint32_t v : {2u, 1u, 2u, 0u, (uint32_t)'#', 0u}) p32(v);
+  size_t l_nm = 0;
+  for (const std::string& nm : names) l_nm += nm.size() + 1;
+  p32((uint32_t)l_nm);
+  for (const std::string& nm : names) {
+    o.insert(o.end(), nm.begin(), nm.end());
+    o.push_back(0);
+  }
+  size_t bi = 0;
+  for (int64_t r = 0; r < nrun; r++) {
+    size_t bj = bi;
+    while (bj < order.size() && (int64_t)(bins[2 * (size_t)order[bj]] >> 16) == r) bj++;
+    p32((uint32_t)(bj - bi));
+    for (; bi < bj; bi++) {
+      const int64_t b = order[bi];
+      const int64_t c0 = (int64_t)bins[2 * (size_t)b + 1];
+      const int64_t c1 = b + 1 < nbin ? (int64_t)bins[2 * (size_t)b + 3] : nchunk;
+      p32((uint32_t)(bins[2 * (size_t)b] & 0xffff));
+      p32((uint32_t)(c1 - c0));
+      for (int64_t c = c0; c < c1; c++) {
+        p64(chunks[2 * (size_t)c]);
+        p64(chunks[2 * (size_t)c + 1]);
+      }
+    }
+    // linear index: an untouched window takes the previous window's offset (leading ones stay 0)
+    const int64_t ni = woff[(size_t)r + 1] - woff[(size_t)r];
+    p32((uint32_t)ni);
+    uint64_t prev = 0;
+    for (int64_t w = 0; w < ni; w++) {
+      const uint64_t v = lin[(size_t)(woff[(size_t)r] + w)];
+      if (v != ~0ull) prev = v;
+      p64(prev);
+    }
+  }
+  uint8_t* b = (uint8_t*)malloc(std::max<size_t>(1, o.size()));
+  if (!b) return DQ_ENOMEM;
+  memcpy(b, o.data(), o.size());
+  *out = b;
+  *out_len = (int64_t)o.size();
   return 0;
 }
 

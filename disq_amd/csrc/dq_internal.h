@@ -43,6 +43,7 @@ enum : int {
   CHK_Z_IMAGE = 12,  // deflate: an emitted word outside the LDS deflate image
   CHK_K3_SPEC = 13,  // K3: the LDS-filtered segment speculation differs from seg_spec_kernel<64>
   CHK_BAI = 14,      // .bai build: a linear window, perm slot, chunk or bin outside its table
+  CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -273,14 +274,17 @@ void launch_bai_level_flags(const uint64_t* key, int64_t n, int la, int64_t* out
 void launch_bai_level_scatter(const uint64_t* key, int64_t n, int la, const int64_t* scan,
                               int64_t base_a, int64_t base_b, int64_t nplaced, int64_t* perm,
                               hipStream_t s);
-// out[j] = (record perm[j] opens a chunk) | (opens a bin) << 32; fin = the final file pointer
+// out[j] = (record perm[j] opens a chunk) | (opens a bin) << 32; fin = the final file pointer.
+// vend (heads and emit): the pointer after record i when it is not the next record's start (text
+// lines with other lines between them, dq_text_write_tbi); nullptr: voff[i + 1], fin after the last
 void launch_bai_heads(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
-                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s);
+                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s,
+                      const uint64_t* vend = nullptr);
 // chunks[2 c], [2 c + 1] = begin, end; bins[2 b], [2 b + 1] = key, first chunk
 void launch_bai_emit(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
                      const int64_t* perm, int64_t nplaced, const int64_t* heads,
                      const int64_t* scan, int64_t nchunk, int64_t nbin, uint64_t* chunks,
-                     uint64_t* bins, hipStream_t s);
+                     uint64_t* bins, hipStream_t s, const uint64_t* vend = nullptr);
 void launch_bs_plus4(const int32_t* bs, int64_t n, int32_t* out, hipStream_t s);
 void launch_add_u64(const uint64_t* in, int64_t n, uint64_t add, uint64_t* out, hipStream_t s);
 void launch_partition_digest2(const uint64_t* hash, PartRange* parts, int64_t nparts,
@@ -352,6 +356,35 @@ void launch_vcf_overlap(const uint8_t* U, const int64_t* vstart, const int32_t* 
 void launch_text_gather(const uint8_t* U, const int64_t* vstart, const int32_t* vlen,
                         const int64_t* kept, const int64_t* out_off, int64_t n, uint8_t* out,
                         hipStream_t s);
+
+// .tbi index build (dq_text_write_tbi, DESIGN.md "Building the .tbi") over the resident lines
+// (term: the nterm terminator ends; nl lines, the last one possibly unterminated).
+enum : int { TBI_ST_FORMAT = 1, TBI_ST_RANGE = 2, TBI_ST_UNSORTED = 3 };  // *status & 0xff
+// flag[k] = line k is a data line (a non-empty value that does not start with '#')
+void launch_tbi_lines(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm, int64_t nl,
+                      int32_t* flag, hipStream_t s);
+// dl[off[k]] = k for the flagged lines (off: exclusive scan of flag; n data lines)
+void launch_tbi_compact(const int32_t* flag, const int64_t* off, int64_t nl, int64_t n, int64_t* dl,
+                        hipStream_t s);
+// Per data line i: pos[i] = POS - 1, endp[i] = end (1-based closed = 0-based exclusive), vs / ve =
+// the virtual offsets of its first byte and of the byte after its terminator, head[i] = its CHROM
+// differs from the previous data line's; *status (all ones) takes the first offender
+// (line index << 8 | TBI_ST_*).
+void launch_tbi_keys(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
+                     const int64_t* dl, int64_t n, const int64_t* uoff, const int64_t* blk_pos,
+                     int64_t nblk, uint64_t fin, int32_t* pos, int32_t* endp, uint64_t* vs,
+                     uint64_t* ve, int32_t* head, unsigned long long* status, hipStream_t s);
+// run = hoff[i] + head[i] - 1 (hoff: exclusive scan of head; nrun runs): key[i] = run << 16 | bin;
+// meta (zero): 5 words per run as launch_bai_keys writes them per reference; per run the data-line
+// and line index of its head and where its CHROM bytes lie in U (nfirst, nline, nstart, nlen).
+void launch_tbi_runs(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
+                     const int64_t* dl, int64_t n, const int32_t* head, const int64_t* hoff,
+                     int64_t nrun, const int32_t* pos, const int32_t* endp, uint64_t* key,
+                     unsigned long long* meta, int64_t* nfirst, int64_t* nline, int64_t* nstart,
+                     int32_t* nlen, hipStream_t s);
+// out[noff[r] ...] = the CHROM bytes of run r (nbytes = noff[nrun])
+void launch_tbi_names(const uint8_t* U, const int64_t* nstart, const int32_t* nlen,
+                      const int64_t* noff, int64_t nrun, int64_t nbytes, uint8_t* out, hipStream_t s);
 
 // DQ_CHECKED: each kernel unit's check words (count << 32 | site bits), read and reset
 uint64_t dq_chk_take_kernels();

@@ -1665,9 +1665,11 @@ __device__ inline int bai_level(uint64_t key) {
   const uint32_t b = (uint32_t)(key & 0xffff);
   return b >= 4681 ? 5 : b >= 585 ? 4 : b >= 73 ? 3 : b >= 9 ? 2 : b >= 1 ? 1 : 0;
 }
-// the virtual offset after record i: the next record's, or the file's final pointer
+// the virtual offset after record i: the next record's, or the file's final pointer (vend: given
+// per record, for text lines that other lines separate)
 __device__ inline uint64_t bai_vend(const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
-                                    int64_t i) {
+                                    int64_t i, const uint64_t* __restrict__ vend = nullptr) {
+  if (vend) return vend[i];
   return i + 1 < n ? voff[i + 1] : fin;
 }
 
@@ -1814,21 +1816,23 @@ __global__ __launch_bounds__(256) void bai_level_scatter_kernel(
 // before it).
 __device__ inline int64_t bai_head(const uint64_t* __restrict__ key,
                                    const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
-                                   const int64_t* __restrict__ perm, int64_t j) {
+                                   const int64_t* __restrict__ perm, int64_t j,
+                                   const uint64_t* __restrict__ vend) {
   const int64_t i = perm[j];
   if (j == 0) return ((int64_t)1 << 32) | 1;
   const int64_t p = perm[j - 1];
   if (key[p] != key[i]) return ((int64_t)1 << 32) | 1;
-  const uint64_t le = bai_vend(voff, n, fin, p) >> 16, vb = voff[i] >> 16;
+  const uint64_t le = bai_vend(voff, n, fin, p, vend) >> 16, vb = voff[i] >> 16;
   return le == vb || le + 1 == vb ? 0 : 1;
 }
 __global__ __launch_bounds__(256) void bai_heads_kernel(const uint64_t* __restrict__ key,
                                                         const uint64_t* __restrict__ voff,
                                                         int64_t n, uint64_t fin,
                                                         const int64_t* __restrict__ perm,
-                                                        int64_t nplaced, int64_t* __restrict__ out) {
+                                                        int64_t nplaced, int64_t* __restrict__ out,
+                                                        const uint64_t* __restrict__ vend) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < nplaced) out[j] = bai_head(key, voff, n, fin, perm, j);
+  if (j < nplaced) out[j] = bai_head(key, voff, n, fin, perm, j, vend);
 }
 // Emit: chunk c = (voffset of its head, end of the last record of its run); bins[2 b] = key,
 // bins[2 b + 1] = the bin's first chunk.  scan = exclusive scan of the heads (chunks low, bins
@@ -1837,14 +1841,14 @@ __global__ __launch_bounds__(256) void bai_emit_kernel(
     const uint64_t* __restrict__ key, const uint64_t* __restrict__ voff, int64_t n, uint64_t fin,
     const int64_t* __restrict__ perm, int64_t nplaced, const int64_t* __restrict__ heads,
     const int64_t* __restrict__ scan, int64_t nchunk, int64_t nbin, uint64_t* __restrict__ chunks,
-    uint64_t* __restrict__ bins) {
+    uint64_t* __restrict__ bins, const uint64_t* __restrict__ vend) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nplaced) return;
   const int64_t i = perm[j], h = heads[j], s = scan[j];
   const int64_t c = (s & 0xffffffff) + (h & 1) - 1, b = (s >> 32) + (h >> 32) - 1;
   DQ_CHK(c >= 0 && c < nchunk && b >= 0 && b < nbin, CHK_BAI);
   if (h & 1) chunks[2 * c] = voff[i];
-  if (j + 1 == nplaced || (heads[j + 1] & 1)) chunks[2 * c + 1] = bai_vend(voff, n, fin, i);
+  if (j + 1 == nplaced || (heads[j + 1] & 1)) chunks[2 * c + 1] = bai_vend(voff, n, fin, i, vend);
   if (h >> 32) {
     bins[2 * b] = key[i];
     bins[2 * b + 1] = (uint64_t)c;
@@ -2448,19 +2452,20 @@ void launch_bai_level_scatter(const uint64_t* key, int64_t n, int la, const int6
 }
 
 void launch_bai_heads(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
-                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s) {
+                      const int64_t* perm, int64_t nplaced, int64_t* out, hipStream_t s,
+                      const uint64_t* vend) {
   if (nplaced <= 0) return;
   hipLaunchKernelGGL(bai_heads_kernel, bai_grid(nplaced), dim3(256), 0, s, key, voff, n, fin, perm,
-                     nplaced, out);
+                     nplaced, out, vend);
 }
 
 void launch_bai_emit(const uint64_t* key, const uint64_t* voff, int64_t n, uint64_t fin,
                      const int64_t* perm, int64_t nplaced, const int64_t* heads,
                      const int64_t* scan, int64_t nchunk, int64_t nbin, uint64_t* chunks,
-                     uint64_t* bins, hipStream_t s) {
+                     uint64_t* bins, hipStream_t s, const uint64_t* vend) {
   if (nplaced <= 0) return;
   hipLaunchKernelGGL(bai_emit_kernel, bai_grid(nplaced), dim3(256), 0, s, key, voff, n, fin, perm,
-                     nplaced, heads, scan, nchunk, nbin, chunks, bins);
+                     nplaced, heads, scan, nchunk, nbin, chunks, bins, vend);
 }
 
 void launch_ranges_to_idx(const int64_t* begin, const int64_t* out_off, int64_t nranges,

@@ -436,7 +436,346 @@ __global__ void vcf_overlap_kernel(const uint8_t* __restrict__ U, const int64_t*
   keep[t] = k;
 }
 
+// ------------------------------------------------------------------ .tbi index build
+// htsjdk TabixIndexCreator / BinningIndexBuilder over the resident lines (DESIGN.md "Building the
+// .tbi", dq_text_write_tbi): the front half that turns data lines into the key / voff / endp / pos
+// arrays of the .bai kernels (dq_kernels.hip), which then build bins, chunks and the linear index.
+struct TLine {
+  int64_t a0;  // the line's first byte (a BOM on line 0 included)
+  int64_t a;   // start of the value (after the BOM)
+  int64_t z;   // end of the value (terminator excluded)
+  int64_t nx;  // the byte after the terminator (ulen for a last line without one)
+};
+__device__ inline TLine tbi_line(const uint8_t* __restrict__ U, int64_t ulen,
+                                 const int64_t* __restrict__ term, int64_t nterm, int64_t k) {
+  TLine L;
+  L.a0 = k == 0 ? 0 : term[k - 1] + 1;
+  if (k < nterm) {
+    const int64_t te = term[k];
+    L.z = (U[te] == '\n' && te > L.a0 && U[te - 1] == '\r') ? te - 1 : te;
+    L.nx = te + 1;
+  } else {
+    L.z = L.nx = ulen;
+  }
+  L.a = L.a0;
+  if (k == 0 && L.z >= 3 && U[0] == 0xEF && U[1] == 0xBB && U[2] == 0xBF) L.a = 3;
+  return L;
+}
+
+__global__ __launch_bounds__(256) void tbi_lines_kernel(const uint8_t* __restrict__ U, int64_t ulen,
+                                                        const int64_t* __restrict__ term,
+                                                        int64_t nterm, int64_t nl,
+                                                        int32_t* __restrict__ flag) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nl) return;
+  const TLine L = tbi_line(U, ulen, term, nterm, k);
+  flag[k] = L.z > L.a && U[L.a] != '#';
+}
+
+__global__ __launch_bounds__(256) void tbi_compact_kernel(const int32_t* __restrict__ flag,
+                                                          const int64_t* __restrict__ off,
+                                                          int64_t nl, int64_t n,
+                                                          int64_t* __restrict__ dl) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nl || !flag[k]) return;
+  const int64_t j = off[k];
+  DQ_CHK(j >= 0 && j < n, CHK_TBI);
+  dl[j] = k;
+}
+
+constexpr int64_t TBI_SAT = (int64_t)1 << 40;  // parsed numbers saturate here (far past 2^29)
+// One thread reads one line, so a byte load of a wave touches 64 cache lines: the line is read in
+// aligned 8-byte words instead (U is 256-byte aligned with 256 readable bytes past ulen).
+__device__ inline uint64_t tbi_load8(const uint8_t* __restrict__ U, int64_t x) {  // 8 bytes at any x
+  const uint64_t* p = reinterpret_cast<const uint64_t*>(U + (x & ~(int64_t)7));
+  const int sh = (int)(x & 7) * 8;
+  const uint64_t lo = p[0];
+  return sh ? (lo >> sh) | (p[1] << (64 - sh)) : lo;
+}
+// bit 7 of every zero byte of w (exact per byte)
+__device__ inline uint64_t tbi_zero_bytes(uint64_t w) {
+  const uint64_t m = 0x7f7f7f7f7f7f7f7full;
+  return ~(((w & m) + m) | w | m);
+}
+// the first byte equal to ch in [x, z), or z (x itself when x >= z)
+__device__ inline int64_t tbi_find(const uint8_t* __restrict__ U, int64_t x, int64_t z, uint8_t ch) {
+  if (x >= z) return x;
+  const uint64_t pat = 0x0101010101010101ull * ch;
+  int64_t base = x & ~(int64_t)7;
+  uint64_t w = *reinterpret_cast<const uint64_t*>(U + base) ^ pat;
+  const int sh = (int)(x & 7) * 8;
+  if (sh) w |= ((uint64_t)1 << sh) - 1;  // the bytes before x match nothing
+  for (;;) {
+    const uint64_t m = tbi_zero_bytes(w);
+    if (m) {
+      const int64_t p = base + (__builtin_ctzll(m) >> 3);
+      return p < z ? p : z;
+    }
+    base += 8;
+    if (base >= z) return z;
+    w = *reinterpret_cast<const uint64_t*>(U + base) ^ pat;
+  }
+}
+// decimal digits of [x, y): the value, *ok = non-empty and digits only
+__device__ inline int64_t tbi_digits(const uint8_t* __restrict__ U, int64_t x, int64_t y, bool* ok) {
+  int64_t v = 0;
+  bool good = x < y;
+  for (; x < y && good; x += 8) {
+    const uint64_t w = tbi_load8(U, x);
+    const int c = (int)min((int64_t)8, y - x);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (j < c && good) {
+        const uint32_t d = (uint32_t)((w >> (8 * j)) & 0xff) - '0';
+        if (d > 9) good = false;
+        else v = min(v * 10 + (int64_t)d, TBI_SAT);
+      }
+    }
+  }
+  *ok = good;
+  return v;
+}
+// [a, a + n) and [b, b + n) hold the same bytes
+__device__ inline bool tbi_same(const uint8_t* __restrict__ U, int64_t a, int64_t b, int64_t n) {
+  for (int64_t o = 0; o < n; o += 8) {
+    uint64_t d = tbi_load8(U, a + o) ^ tbi_load8(U, b + o);
+    if (n - o < 8) d &= ((uint64_t)1 << (8 * (n - o))) - 1;
+    if (d) return false;
+  }
+  return true;
+}
+
+struct TRec {
+  int64_t c1;        // end of CHROM (the first tab, or the value's end)
+  int64_t pos, end;  // POS and the end (1-based, closed), end >= pos
+  bool ok;           // at least 4 fields, a CHROM, a decimal POS
+};
+// CHROM, POS, REF and the INFO END of the value [a, z): nothing past the INFO field is read
+__device__ inline TRec tbi_parse(const uint8_t* __restrict__ U, int64_t a, int64_t z) {
+  TRec R;
+  R.ok = false;
+  R.pos = R.end = 0;
+  R.c1 = tbi_find(U, a, z, '\t');
+  if (R.c1 == a || R.c1 >= z) return R;
+  const int64_t f2 = tbi_find(U, R.c1 + 1, z, '\t');  // end of POS
+  if (f2 >= z) return R;
+  const int64_t f3 = tbi_find(U, f2 + 1, z, '\t');    // end of ID
+  if (f3 >= z) return R;
+  bool num = false;
+  R.pos = tbi_digits(U, R.c1 + 1, f2, &num);
+  if (!num) return R;
+  int64_t g = tbi_find(U, f3 + 1, z, '\t');           // end of REF
+  R.end = R.pos + (g - (f3 + 1)) - 1;
+  int nf = 4;
+  while (nf < 7 && g < z) {                           // ALT, QUAL, FILTER
+    g = tbi_find(U, g + 1, z, '\t');
+    nf++;
+  }
+  if (nf == 7 && g < z) {
+    const int64_t i0 = g + 1, i1 = tbi_find(U, i0, z, '\t');  // INFO
+    const uint32_t key = 'E' | 'N' << 8 | 'D' << 16 | (uint32_t)'=' << 24;
+    for (int64_t x = i0; x + 4 <= i1; x = tbi_find(U, x, i1, ';') + 1) {  // x: the start of a key
+      if ((uint32_t)tbi_load8(U, x) != key) continue;
+      int64_t y = x + 4;                                     // the first END key decides
+      const int64_t ye = tbi_find(U, y, i1, ';');
+      bool neg = false, okv = false;
+      if (y < ye && (U[y] == '-' || U[y] == '+')) neg = U[y++] == '-';
+      const int64_t e = tbi_digits(U, y, ye, &okv);
+      if (okv) R.end = neg ? -e : e;
+      break;
+    }
+  }
+  if (R.end < R.pos) R.end = R.pos;
+  R.ok = true;
+  return R;
+}
+
+// the block holding byte x < ulen of U: the last block starting at or before x (the non-empty one)
+__device__ inline int64_t tbi_block(const int64_t* __restrict__ uoff, int64_t nblk, int64_t x) {
+  int64_t lo = 0, hi = nblk;  // first block with uoff > x
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (uoff[mid] <= x) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t b = lo - 1;
+  DQ_CHK(b >= 0 && b < nblk && x - uoff[b >= 0 ? b : 0] < 65536, CHK_TBI);
+  return b < 0 ? 0 : b;
+}
+
+__device__ inline int32_t tbi_reg2bin(int32_t beg, int32_t end) {  // SAMv1 section 5.3
+  --end;
+  if (beg >> 14 == end >> 14) return 4681 + (beg >> 14);
+  if (beg >> 17 == end >> 17) return 585 + (beg >> 17);
+  if (beg >> 20 == end >> 20) return 73 + (beg >> 20);
+  if (beg >> 23 == end >> 23) return 9 + (beg >> 23);
+  if (beg >> 26 == end >> 26) return 1 + (beg >> 26);
+  return 0;
+}
+
+// Keys, one thread per data line: fields, file pointers, the run-head flag (CHROM bytes differ from
+// the previous data line's) and the checks against that line.  The first offender goes into
+// *status by atomic min (line index << 8 | TBI_ST_*; of one line's faults the lowest code).
+__global__ __launch_bounds__(256) void tbi_keys_kernel(
+    const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ term, int64_t nterm,
+    const int64_t* __restrict__ dl, int64_t n, const int64_t* __restrict__ uoff,
+    const int64_t* __restrict__ blk_pos, int64_t nblk, uint64_t fin, int32_t* __restrict__ pos,
+    int32_t* __restrict__ endp, uint64_t* __restrict__ vs, uint64_t* __restrict__ ve,
+    int32_t* __restrict__ head, unsigned long long* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t k = dl[i];
+  const TLine L = tbi_line(U, ulen, term, nterm, k);
+  const TRec R = tbi_parse(U, L.a, L.z);
+  unsigned long long bad = 0;
+  if (!R.ok) bad = TBI_ST_FORMAT;
+  else if (R.pos < 1 || R.end > ((int64_t)1 << 29)) bad = TBI_ST_RANGE;
+  int32_t hd = 1;
+  if (i > 0) {
+    const TLine P = tbi_line(U, ulen, term, nterm, dl[i - 1]);
+    const int64_t p1 = tbi_find(U, P.a, P.z, '\t');
+    const bool same = p1 - P.a == R.c1 - L.a && tbi_same(U, P.a, L.a, R.c1 - L.a);
+    hd = !same;
+    if (same && !bad && p1 < P.z) {  // a malformed previous line is its own, earlier offender
+      bool num = false;
+      const int64_t pp = tbi_digits(U, p1 + 1, tbi_find(U, p1 + 1, P.z, '\t'), &num);
+      if (num && pp > R.pos) bad = TBI_ST_UNSORTED;
+    }
+  }
+  if (bad) atomicMin(status, (unsigned long long)k << 8 | bad);
+  pos[i] = bad ? 0 : (int32_t)(R.pos - 1);
+  endp[i] = bad ? 1 : (int32_t)R.end;
+  // virtual offsets: the block's address << 16 | the offset in the block; the line's end lies in
+  // the same block unless the line crosses into a later one, and past the stream it is fin
+  const int64_t b = tbi_block(uoff, nblk, L.a0);
+  vs[i] = ((uint64_t)blk_pos[b] << 16) | (uint64_t)(L.a0 - uoff[b]);
+  uint64_t e = fin;
+  if (L.nx < ulen) {
+    const int64_t b2 = L.nx < uoff[b + 1] ? b : tbi_block(uoff, nblk, L.nx);
+    e = ((uint64_t)blk_pos[b2] << 16) | (uint64_t)(L.nx - uoff[b2]);
+  }
+  ve[i] = e;
+  head[i] = hd;
+}
+
+// Runs: run = rank of the line's run head; key = run << 16 | bin.  meta[5 run + 0..4] = ~(first
+// data line), last data line + 1, lines, 0, last linear window + 1 (the layout of
+// bai_keys_kernel).  The last window is a maximum over the run, wave-reduced so that one lane per
+// distinct run of the wave issues the atomic; a run is a contiguous range of data lines, so the
+// other words follow from the heads' positions (tbi_meta_kernel) without atomics on one address.
+// A run's head records its data-line and line index and where its CHROM bytes lie.
+__global__ __launch_bounds__(256) void tbi_runs_kernel(
+    const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ term, int64_t nterm,
+    const int64_t* __restrict__ dl, int64_t n, const int32_t* __restrict__ head,
+    const int64_t* __restrict__ hoff, int64_t nrun, const int32_t* __restrict__ pos,
+    const int32_t* __restrict__ endp, uint64_t* __restrict__ key,
+    unsigned long long* __restrict__ meta, int64_t* __restrict__ nfirst,
+    int64_t* __restrict__ nline, int64_t* __restrict__ nstart, int32_t* __restrict__ nlen) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool act = i < n;
+  int32_t run = -1, we = -1;
+  if (act) {
+    const int32_t hd = head[i];
+    const int64_t r = hoff[i] + hd - 1;
+    DQ_CHK(r >= 0 && r < nrun, CHK_TBI);
+    if (r < 0 || r >= nrun) {
+      act = false;
+    } else {
+      run = (int32_t)r;
+      const int32_t e = endp[i];
+      key[i] = (uint64_t)r << 16 | (uint64_t)tbi_reg2bin(pos[i], e);
+      we = (e - 1) >> 14;
+      if (hd) {
+        const int64_t k = dl[i];
+        const TLine L = tbi_line(U, ulen, term, nterm, k);
+        nfirst[r] = i;
+        nline[r] = k;
+        nstart[r] = L.a;
+        nlen[r] = (int32_t)min(tbi_find(U, L.a, L.z, '\t') - L.a, (int64_t)INT32_MAX);
+      }
+    }
+  }
+  uint64_t rem = __ballot(act);
+  while (rem) {
+    const int l = __builtin_ctzll(rem);
+    const int32_t r = __shfl(run, l);
+    const bool mine = act && run == r;
+    const uint64_t m = __ballot(mine);
+    int32_t wmax = mine ? we : -1;
+    for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_xor(wmax, o));
+    if (lane == l) atomicMax(meta + 5 * (int64_t)r + 4, (unsigned long long)(wmax + 1));
+    rem &= ~m;
+  }
+}
+__global__ __launch_bounds__(256) void tbi_meta_kernel(const int64_t* __restrict__ nfirst,
+                                                       int64_t nrun, int64_t n,
+                                                       unsigned long long* __restrict__ meta) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrun) return;
+  const int64_t first = nfirst[r], last1 = r + 1 < nrun ? nfirst[r + 1] : n;
+  DQ_CHK(first >= 0 && first < last1 && last1 <= n, CHK_TBI);
+  meta[5 * r + 0] = ~(unsigned long long)first;
+  meta[5 * r + 1] = (unsigned long long)last1;
+  meta[5 * r + 2] = (unsigned long long)(last1 - first);
+}
+
+__global__ __launch_bounds__(256) void tbi_names_kernel(const uint8_t* __restrict__ U,
+                                                        const int64_t* __restrict__ nstart,
+                                                        const int32_t* __restrict__ nlen,
+                                                        const int64_t* __restrict__ noff,
+                                                        int64_t nrun, int64_t nbytes,
+                                                        uint8_t* __restrict__ out) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrun) return;
+  const int64_t a = nstart[r], o = noff[r], len = noff[r + 1] - o;  // 0: the host left the run out
+  DQ_CHK(o >= 0 && len >= 0 && len <= nlen[r] && o + len <= nbytes, CHK_TBI);
+  if (o < 0 || o + len > nbytes) return;
+  for (int64_t x = 0; x < len; x++) out[o + x] = U[a + x];
+}
+
 }  // namespace
+
+static inline dim3 tbi_grid(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+void launch_tbi_lines(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm, int64_t nl,
+                      int32_t* flag, hipStream_t s) {
+  if (nl <= 0) return;
+  hipLaunchKernelGGL(tbi_lines_kernel, tbi_grid(nl), dim3(256), 0, s, U, ulen, term, nterm, nl, flag);
+}
+
+void launch_tbi_compact(const int32_t* flag, const int64_t* off, int64_t nl, int64_t n, int64_t* dl,
+                        hipStream_t s) {
+  if (nl <= 0) return;
+  hipLaunchKernelGGL(tbi_compact_kernel, tbi_grid(nl), dim3(256), 0, s, flag, off, nl, n, dl);
+}
+
+void launch_tbi_keys(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
+                     const int64_t* dl, int64_t n, const int64_t* uoff, const int64_t* blk_pos,
+                     int64_t nblk, uint64_t fin, int32_t* pos, int32_t* endp, uint64_t* vs,
+                     uint64_t* ve, int32_t* head, unsigned long long* status, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(tbi_keys_kernel, tbi_grid(n), dim3(256), 0, s, U, ulen, term, nterm, dl, n,
+                     uoff, blk_pos, nblk, fin, pos, endp, vs, ve, head, status);
+}
+
+void launch_tbi_runs(const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
+                     const int64_t* dl, int64_t n, const int32_t* head, const int64_t* hoff,
+                     int64_t nrun, const int32_t* pos, const int32_t* endp, uint64_t* key,
+                     unsigned long long* meta, int64_t* nfirst, int64_t* nline, int64_t* nstart,
+                     int32_t* nlen, hipStream_t s) {
+  if (n <= 0 || nrun <= 0) return;
+  hipLaunchKernelGGL(tbi_runs_kernel, tbi_grid(n), dim3(256), 0, s, U, ulen, term, nterm, dl, n,
+                     head, hoff, nrun, pos, endp, key, meta, nfirst, nline, nstart, nlen);
+  hipLaunchKernelGGL(tbi_meta_kernel, tbi_grid(nrun), dim3(256), 0, s, nfirst, nrun, n, meta);
+}
+
+void launch_tbi_names(const uint8_t* U, const int64_t* nstart, const int32_t* nlen,
+                      const int64_t* noff, int64_t nrun, int64_t nbytes, uint8_t* out, hipStream_t s) {
+  if (nrun <= 0) return;
+  hipLaunchKernelGGL(tbi_names_kernel, tbi_grid(nrun), dim3(256), 0, s, U, nstart, nlen, noff, nrun,
+                     nbytes, out);
+}
 
 void launch_vcf_overlap(const uint8_t* U, const int64_t* vstart, const int32_t* vlen, int64_t n,
                         const uint8_t* names, const int32_t* noff, int32_t nnames,

@@ -381,6 +381,51 @@ class HtsjdkVariantsRddStorage:
                  for p in range(len(po) - 1)]
         return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(parts))
 
+    def write(self, rdd: HtsjdkVariantsRdd, path: str, tempPartsDirectory: Optional[str] = None, *,
+              tabix: bool = False):
+        """VcfSink.save (D/impl/formats/vcf/VcfSink.java:27-68) with GPU BGZF compression: the
+        header lines as read (getHeader(), each followed by a newline) as their own BGZF blocks,
+        each partition's lines with a newline after each (as TextOutputFormat writes them) as a
+        BGZF part without the EOF terminator, the 28-byte EOF block, then the parts merged in partition order
+        (Merger.mergeParts) into `path`; the temporary parts directory is deleted after the merge.
+        The output is compressed when `path` ends in .bgz or .gz and a plain concatenation for
+        .vcf; any other extension raises ValueError (VcfSink's format lookup).
+
+        tabix: after the merge the written file is opened on the device and indexed into
+        `path + ".tbi"` (dq_text_write_tbi; the variants must be sorted).  It stands in for the
+        TabixIndexWriteOption of later Disq versions and needs a compressed path; with the
+        default nothing but `path` is written."""
+        compressed = path.endswith(".bgz") or path.endswith(".gz")
+        if not compressed and not path.endswith(".vcf"):
+            raise ValueError(f"Cannot find format extension for {path}")
+        if tabix and not compressed:
+            raise ValueError(f"{path}: a tabix index needs a BGZF-compressed VCF (.vcf.gz/.vcf.bgz)")
+        texts = [b"".join(bytes(h) + b"\n" for h in rdd.getHeader())]
+        for p in rdd.getVariants().partitions:
+            texts.append(b"".join(bytes(l) + b"\n" for l in p))
+        if compressed:
+            eof = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+            with _lib.Context(device=self._device) as ctx:
+                pieces = [ctx.bgzf_compress(t) for t in texts] + [eof]
+            names = ["header"] + [f"part-r-{i:05d}" for i in range(len(texts) - 1)] + ["terminator"]
+        else:
+            pieces = texts
+            names = ["header"] + [f"part-r-{i:05d}" for i in range(len(texts) - 1)]
+        if tempPartsDirectory:
+            os.makedirs(tempPartsDirectory, exist_ok=True)
+            for n, d in zip(names, pieces):
+                with open(os.path.join(tempPartsDirectory, n), "wb") as fh:
+                    fh.write(d)
+        with open(path, "wb") as fh:
+            for d in pieces:
+                fh.write(d)
+        if tempPartsDirectory:  # fileSystemWrapper.delete(tempPartsDirectory)
+            import shutil
+            shutil.rmtree(tempPartsDirectory, ignore_errors=True)
+        if tabix:
+            TabixIndexer.createIndex(path, device=self._device)
+        return path
+
 
 def vcf_header_lines(path: str):
     """The leading '#' lines of a BGZF VCF, read from a prefix of the file: BGZF members are
@@ -461,4 +506,23 @@ class BAMIndexer:
             data = ctx.write_bai()
         with open(output, "wb") as fh:
             fh.write(data)
+        return output
+
+
+class TabixIndexer:
+    """htsjdk TabixIndexCreator on the GPU text path (dq_text_write_tbi): the .tbi of a sorted
+    BGZF-compressed VCF, built from the resident lines and written, as htsjdk writes it, as a BGZF
+    file (the index bytes in BGZF blocks, then the EOF block)."""
+
+    @staticmethod
+    def createIndex(vcfFile: str, output: Optional[str] = None, device: int = 0) -> str:
+        if output is None:
+            output = vcfFile + ".tbi"  # TabixUtils.STANDARD_INDEX_EXTENSION
+        with _lib.Context(device=device) as ctx:
+            ctx.text_open_path(vcfFile)
+            data = ctx.text_write_tbi()
+            packed = ctx.bgzf_compress(data)
+        with open(output, "wb") as fh:
+            fh.write(packed)
+            fh.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
         return output

@@ -377,6 +377,16 @@ int dq_text_open_path(dq_ctx* ctx, const char* path);
 int dq_text_run(dq_ctx* ctx, int32_t drop_header_lines, dq_stats* stats);
 int dq_text_read(dq_ctx* ctx, int32_t drop_header_lines, dq_text_batch** out);
 void dq_text_batch_free(dq_text_batch* b);
+/* htsjdk TabixIndexCreator for the open (whole) VCF text file: the DECOMPRESSED tabix bytes, the
+ * form dq_text_set_index takes (a .tbi on disk is these bytes as a BGZF file; the rules are in
+ * DESIGN.md "Building the .tbi").  Every data line of the file is indexed exactly once, whatever
+ * split_size, use_nio, a set index or set intervals say; the context reads as before afterwards.
+ * A data line that is not a VCF record, a POS below 1 or an end beyond 2^29, or a file that is
+ * not sorted (POS going down inside a contig, a contig coming back) gives DQ_EFORMAT naming the
+ * first offender's 0-based line index; no open text file gives DQ_EINVAL.  *out is
+ * library-allocated (dq_free); *ms (may be NULL) = device time of the index build alone, after
+ * scan, inflate and the terminator scan. */
+int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms);
 
 /* ---- BGZF compression: the write path -----------------------
  * Replaces htsjdk BlockCompressedOutputStream under HeaderlessBamOutputFormat.BamRecordWriter

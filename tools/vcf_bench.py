@@ -79,7 +79,10 @@ def _compress_job(args):
     return b"".join(_bgzf_member(_TEXT[a:min(a + BLOCK_U, hi)]) for a in range(lo, hi, BLOCK_U))
 
 
-def make_vcf(mb: int, samples: int, procs: int):
+def make_vcf(mb: int, samples: int, procs: int, tabix_range: bool = False):
+    """(text, BGZF bytes).  tabix_range: positions restart on every contig, so that they stay
+    below 2^29, the limit of a tabix index (tools/tbi_bench.py); the default numbers the 7 Mb
+    stretches through the whole file."""
     header = ["##fileformat=VCFv4.2", '##FILTER=<ID=PASS,Description="All filters passed">']
     header += ["##contig=<ID=%s,length=%d>" % c for c in CONTIGS]
     header += ['##INFO=<ID=%s,Number=1,Type=Float,Description="%s">' % (k, k)
@@ -95,6 +98,13 @@ def make_vcf(mb: int, samples: int, procs: int):
     jobs = [(1000 + k, min(per_job, n_lines - k * per_job), samples,
              CONTIGS[(k * len(CONTIGS)) * per_job // n_lines][0], 10_000 + k * 7_000_000)
             for k in range((n_lines + per_job - 1) // per_job)]
+    if tabix_range:
+        first = {}
+        for k, j in enumerate(jobs):
+            first.setdefault(j[3], k)
+        jobs = [j[:4] + (10_000 + (k - first[j[3]]) * 7_000_000,) for k, j in enumerate(jobs)]
+        if max(j[4] for j in jobs) + 8_000_000 > 1 << 29:
+            raise ValueError("too many lines per contig for positions below 2^29")
     global _TEXT
     with Pool(procs) as p:
         text = head + b"".join(p.map(_chunk_job, jobs))
