@@ -85,6 +85,14 @@ constexpr int OUTCAP = 65536 + 24;  // + alignment shift (<= 15) + descriptor ov
 #ifndef DQ_RES_G
 #define DQ_RES_G 1
 #endif
+// DQ_RES_QUAD (round 7): the first hop by groups of four contiguous bytes, whose (at most two)
+// owners one search of the bitmap finds.  At the product shape (WG = 512, NB = 4, G = 1) only the
+// first hop works by groups; at -DDQ_RES_G=4 -DDQ_RES_NB=1 the jump rounds and steps do too (a
+// group's next pointers and bytes in one store).  DQ_RES_QUAD = 0: the per-byte first hop of
+// round 6 at every shape.
+#ifndef DQ_RES_QUAD
+#define DQ_RES_QUAD 1
+#endif
 constexpr int RES_NXT = DQ_RES_NB * DQ_RES_G * WG;  // resolve batch bytes (NB * G * WG)
 constexpr int NCARRY = (65536 + RES_NXT - 1) / RES_NXT + 1;  // batches of a block (carry slots)
 
@@ -1526,16 +1534,111 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
   constexpr bool CSTEP = (DQ_CSTEP != 0 && G > 1) || CH % 512 != 0;
   static_assert(BATCH <= RES_NXT, "the batch's next-pointers fit the resolve scratch");
   static_assert((65536 + BATCH - 1) / BATCH <= NCARRY, "one carry slot per batch");
+  static_assert(CSTEP || CH / 512 <= G, "the G ordered steps of a chunk cover it");
+  // QUAD: the four contiguous bytes of a thread as one group (one owner search, two descriptors,
+  // one 64-bit store of its four next pointers)
+  constexpr bool QUAD = G == 4 && DQ_RES_QUAD != 0;
+  // HYB: one byte per thread and chunk in the jump rounds and steps (a wave whose bytes are all
+  // final skips its jump rounds, a step is one byte read and write per thread), but the first
+  // hop by groups: thread t resolves bytes 4t .. 4t + 3 of the batch and publishes their next
+  // pointers; after the barrier every thread adopts the pointers of its own bytes from nxt
+  constexpr bool HYB = G == 1 && NB == 4 && WG == 512 && !CSTEP && DQ_RES_QUAD != 0;
+  constexpr int GK = HYB ? 1 : NB, GCH = HYB ? BATCH : CH;  // groups per thread, their stride
+  static_assert(!(QUAD || HYB) || offsetof(LdsI, u.r.nxt) % 8 == 0, "a group's next pointers are one 64-bit word");
+  constexpr bool INR = 65536 % BATCH == 0;  // no batch reaches past the largest block
   uint16_t* nxt = L.u.r.nxt;
+  auto pack16 = [](int32_t lo, int32_t hi) {  // lo | hi << 16 of two 16-bit values: one v_perm
+    return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
+  };
+  auto med3 = [](int32_t a, int32_t b, int32_t c) { return max(min(a, b), min(max(a, b), c)); };
+  // four next pointers at the 8-byte-aligned index `off` as one ds_write_b64 (a memcpy: the
+  // 16-bit reads of nxt alias it)
+  auto store_nxt4 = [&](int off, uint32_t lo, uint32_t hi) {
+    const uint2 v = make_uint2(lo, hi);
+    __builtin_memcpy(__builtin_assume_aligned(nxt + off, 8), &v, 8);
+  };
   // (a) sources of batch `b0`.  First hop, every byte: its owner (one 64-bit bitmap word, one
   //     last_start) and the owner's descriptor give the copy source (G <= 4 bytes have at most
   //     two owners: matches are >= 3 bytes long).  A source before the byte's 512-byte step is
   //     final (that step is complete when (b) reaches this one); so is a literal.  Every byte
   //     publishes its source in nxt.  The match straddling the batch start is the carry (cms,
-  //     cdesc): its descriptor lies before the batch.
+  //     cdesc): its descriptor lies before the batch.  DQ_RES_QUAD (the product build): the first
+  //     hop works on groups of four contiguous bytes, thread t on bytes 4t .. 4t + 3 of the batch
+  //     (one owner search and two descriptor decodes for four bytes, 163 -> 97 VALU per thread and
+  //     batch); with one byte per thread in the steps (HYB) each thread then adopts its own
+  //     bytes' pointers from nxt after the barrier that follows (21 VALU).
   auto first_hop = [&](int32_t b0, int32_t cms, uint32_t cdesc, int32_t* fr, int32_t* xs,
                        bool& pending) {
     pending = false;
+    if constexpr (QUAD || HYB) {
+      // Bytes g0 .. g0 + 3 lie in one bitmap word and have at most two owners: A, the match live
+      // at byte 0 (a start at g0, else the last start before the group), and B, the match live
+      // at byte 3 (the group's highest start, else A).  The group's start bits are one of
+      // 0, 1, 2, 4, 8 or 9: a match is >= 3 bytes long.  One search and two descriptor decodes
+      // per group; a byte selects its owner's end and distance by x >= B.
+#pragma unroll
+      for (int k = 0; k < GK; k++) {
+        const int32_t g0 = b0 + k * GCH + 4 * t;
+        const int w = INR ? g0 >> 6 : min(g0 >> 6, 1023);  // bytes past rsize: copy = false
+        DQ_CHK(w >= 0 && w < 1024, CHK_K2_LAST);
+        const uint64_t m = bm64[w];
+        const int32_t ls = w ? (int32_t)zx16(L.u.r.last_start[w - 1]) : 0xffff;
+        const uint32_t bit = (uint32_t)g0 & 60u;
+        const uint64_t below = m & ~(~0ull << bit);  // the word's starts before the group
+        const int32_t prev = below ? (g0 | 63) - (int32_t)__clzll(below) : ls;
+        const uint32_t nib = (uint32_t)(m >> bit) & 15u;
+        DQ_CHK(g0 >= rsize || ((0x0317u >> nib) & 1u), CHK_K2_BM);  // nibbles 0, 1, 2, 4, 8, 9
+        const bool hasB = nib != 0;
+        const int32_t A = (nib & 1u) ? g0 : prev;
+        const int32_t Bs = hasB ? g0 + 31 - (int32_t)__clz(nib) : A;
+        // (an owner before the batch reads a stale descriptor, in range and unused: the carry's
+        // is taken instead; B's is used only when B starts in the group)
+        const uint32_t ldA = load_desc(L, sh + (INR ? A : min(A, 65535)));
+        const uint32_t ldB = load_desc(L, sh + (INR ? Bs : min(Bs, 65535)));
+        // A before the batch is the last start before it, so it is the carry or a match that
+        // ended before the batch: the carry's descriptor, or 0 (3 bytes: it ends before b0 too).
+        // lim = the owner's length cut at rsize, 0 for "no start yet" (0xffff, which only A can
+        // be), so a byte copies when (unsigned)(x - owner) < lim
+        const uint32_t dA = A < b0 ? cdesc : ldA;
+        const uint32_t dB = hasB ? ldB : dA;
+        const int32_t D1A = (int32_t)(dA & 0x7fff), D1B = (int32_t)(dB & 0x7fff);  // D - 1
+        const int32_t remA = A == 0xffff ? 0 : rsize - A;
+        const int32_t limA = med3(remA, 0, (int32_t)(dA >> 15) + 3);
+        const int32_t limB = med3(hasB ? rsize - Bs : remA, 0, (int32_t)(dB >> 15) + 3);
+        const int32_t sbk = b0 + k * GCH + (CSTEP ? 0 : ((4 * t) & ~511));
+        int32_t f4[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int32_t x = g0 + i;
+          const bool useB = i == 0 ? false : i == 3 ? true : x >= Bs;  // by definition of A, B
+          const int32_t ms = useB ? Bs : A, lim = useB ? limB : limA, D1 = useB ? D1B : D1A;
+          // src = ms - D + (x - ms) mod D; x - ms <= 257: a float reciprocal + one fix-up is
+          // exact, needed only by bytes past the first period of an overlapping match (skipped
+          // per wave); otherwise src = x - D = (D1 ^ ~0) + x, one v_xad
+          const int32_t jj = x - ms;
+          const bool copy = (uint32_t)jj < (uint32_t)lim;
+          int32_t src = (int32_t)((uint32_t)D1 ^ ~0u) + x;
+          if (__builtin_expect(__any(copy && jj > D1), 0)) {
+            const int32_t D = D1 + 1;
+            const int32_t q = (int32_t)((float)jj * __builtin_amdgcn_rcpf((float)D));
+            int32_t r = jj - q * D;
+            r = r >= D ? r - D : r;
+            src = ms - D + r;
+          }
+          DQ_CHK(!copy || (src >= 0 && src < x), CHK_K2_SRC);
+          f4[i] = copy ? src : x;
+          if constexpr (QUAD) {
+            const bool done = !copy || src < sbk;
+            fr[4 * k + i] = f4[i];
+            xs[4 * k + i] = done ? x : src;  // a final entry points at its own byte (see jump_round)
+            pending = pending || !done;
+          }
+        }
+        DQ_CHK(k * GCH + 4 * t + 3 < BATCH, CHK_K2_NXT);
+        store_nxt4(k * GCH + 4 * t, pack16(f4[0], f4[1]), pack16(f4[2], f4[3]));
+      }
+      return;
+    }
     uint64_t mw[NB];
     int32_t lsv[NB];
 #pragma unroll
@@ -1594,6 +1697,24 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       }
     }
   };
+  // HYB, after the barrier that follows the first hop: every thread takes the first-hop sources
+  // of its own bytes from nxt (only their owner rewrites them from here on)
+  auto adopt = [&](int32_t b0, int32_t* fr, int32_t* xs, bool& pending) {
+    int32_t qv[NE];
+#pragma unroll
+    for (int e = 0; e < NE; e++) qv[e] = (int32_t)zx16(nxt[(e / G) * CH + G * t + e % G]);
+    pending = false;
+#pragma unroll
+    for (int e = 0; e < NE; e++) {
+      const int32_t x = b0 + (e / G) * CH + G * t + e % G;
+      const int32_t sbk = b0 + (e / G) * CH + ((G * t) & ~511);
+      const int32_t q = qv[e];
+      const bool done = q == x || q < sbk;  // a literal, or a source before the byte's step
+      fr[e] = q;
+      xs[e] = done ? x : q;
+      pending = pending || !done;
+    }
+  };
   // Pointer jumping inside the byte's step: a pending byte reads nxt at its current source and
   // publishes how far it got, so a byte that reads an advanced pointer skips that byte's chain.
   // Every value read is a byte of the same chain, so no barrier orders the rounds and each read
@@ -1621,7 +1742,12 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       fr[e] = fin ? q : fr[e];
       xs[e] = go ? q : b0 + own;
       any = any || go;
-      nxt[own] = (uint16_t)q;
+      if constexpr (!QUAD) nxt[own] = (uint16_t)q;
+    }
+    if constexpr (QUAD) {  // a group's four pointers are one aligned 64-bit word (q < 65536)
+#pragma unroll
+      for (int k = 0; k < NB; k++)
+        store_nxt4(k * CH + 4 * t, pack16(qv[4 * k], qv[4 * k + 1]), pack16(qv[4 * k + 2], qv[4 * k + 3]));
     }
     pending = any;
   };
@@ -1654,6 +1780,7 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     L.u.r.carry_desc[t] = ncdesc;
   }
   __syncthreads();
+  if constexpr (HYB) adopt(0, frA, xsA, pendA);
   for (int hop = 0; pendA && hop < WG + 2; hop++) jump_round(0, frA, xsA, pendA);
   for (int32_t bs = 0; bs < rsize; bs += BATCH) {
     const uint64_t tb0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
@@ -1680,13 +1807,38 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
 #pragma unroll
           for (int i = 0; i < G; i++) {
             DQ_CHK(g0 + i >= rsize || (frA[k * G + i] >= 0 && frA[k * G + i] <= g0 + i), CHK_K2_SRC);
-            v[i] = O[min(frA[k * G + i], 65535)];
+            v[i] = O[INR ? frA[k * G + i] : min(frA[k * G + i], 65535)];
           }
+        if constexpr (HYB)  // the first barrier after the next batch's first hop has passed
+          if (k == 1 && more) adopt(nbs, frB, xsB, pendB);
         if ((k > 0 || j > 0) && pendB) jump_round(nbs, frB, xsB, pendB);
-        if (mine)
+        if constexpr (QUAD && INR) {
+          // the group's four bytes in one to three stores by the image's alignment (uniform): a
+          // byte at or past rsize is its own source, so it rewrites its own value like a literal
+          if (mine) {
+            const uint32_t lo = (uint32_t)v[0] | (uint32_t)v[1] << 8;
+            const uint32_t hi = (uint32_t)v[2] | (uint32_t)v[3] << 8;
+            uint8_t* const p = L.out + sh + g0;
+            if ((sh & 3) == 0) {
+              const uint32_t w4 = lo | hi << 16;
+              __builtin_memcpy(__builtin_assume_aligned(p, 4), &w4, 4);
+            } else if ((sh & 3) == 2) {
+              const uint16_t a2 = (uint16_t)lo, b2 = (uint16_t)hi;
+              __builtin_memcpy(__builtin_assume_aligned(p, 2), &a2, 2);
+              __builtin_memcpy(__builtin_assume_aligned(p + 2, 2), &b2, 2);
+            } else {
+              const uint16_t m2 = (uint16_t)(v[1] | v[2] << 8);
+              p[0] = v[0];
+              __builtin_memcpy(__builtin_assume_aligned(p + 1, 2), &m2, 2);
+              p[3] = v[3];
+            }
+          }
+        } else {
+          if (mine)
 #pragma unroll
-          for (int i = 0; i < G; i++)
-            if (g0 + i < rsize) L.out[sh + g0 + i] = v[i];  // a literal rewrites its own value
+            for (int i = 0; i < G; i++)
+              if (g0 + i < rsize) L.out[sh + g0 + i] = v[i];  // a literal rewrites its own value
+        }
         __syncthreads();
       }
     }

@@ -33,7 +33,8 @@ enum : int {
   CHK_K2_IMAGE = 2,  // K2: an emit / stored-copy store outside the LDS output image
   CHK_K2_TABLE = 3,  // K2: a second-level table read outside its alphabet's area
   CHK_K2_LANES = 4,  // K2: per-lane arrays / redo list outside the image tail
-  CHK_K2_BM = 5,     // K2: a match-start bitmap word outside the bitmap
+  CHK_K2_BM = 5,     // K2: a match-start bitmap word outside the bitmap, or a resolve group of four
+                     //     bytes whose start bits are not 0, 1, 2, 4, 8 or 9 (matches are >= 3 long)
   CHK_K2_NXT = 6,    // K2: a resolve next pointer outside the batch window
   CHK_K2_SRC = 7,    // K2: a resolve copy source outside [0, isize)
   CHK_K3_STAGE = 8,  // K3: a record's staged bytes (or their reads) outside the LDS staging

@@ -6,6 +6,13 @@ the warm-up none of these.  Only loops with two global loads (the two refills of
 and the common-path (non-SLOW) instantiation are listed.
 
   python tools/isa_loops.py [extra hipcc flags...]
+  python tools/isa_loops.py --resolve [extra hipcc flags...]
+
+--resolve: the resolve's batch loop (the depth-1 loop with the match-start search, v_ffbh, and the
+step barriers) split by basic block into the next batch's first hop (up to the first step's byte
+reads), the jump rounds (blocks that read a next pointer per entry: the scheduler may merge a
+step's byte read or store into them), the U store and the rest of the ordered steps.  Counts are
+per thread and batch; the rare modulo path (v_rcp_f32) is listed apart.
 """
 import os
 import re
@@ -61,7 +68,61 @@ def classify(body):
     return "warm-up"
 
 
+def resolve(ker):
+    best = None
+    for name, body in loops(ker):
+        if (any(x.startswith("v_ffbh") for x in body) and any(x.startswith("ds_read_u16") for x in body)
+                and sum(x.startswith("s_barrier") for x in body) >= 2):
+            if best is None or len(body) > len(best[1]):
+                best = (name, body)
+    a = next(i for i, l in enumerate(ker) if l.startswith(best[0] + ":"))
+    blocks, cur = [], None
+    n = 0
+    for l in ker[a:]:
+        m = re.match(r"^(\.LBB\d+_\d+):", l)
+        if m:
+            cur = [m.group(1), []]
+            blocks.append(cur)
+            continue
+        x = l.strip()
+        if x and not x.startswith((";", ".")):
+            cur[1].append(x)
+            n += 1
+            if n >= len(best[1]):
+                break
+    cnt = lambda b, op: sum(x.startswith(op) for x in b)  # noqa: E731
+    state, tot, rounds = "first hop", {}, []
+    print(f"resolve batch loop {best[0]}: {len(best[1])} instructions")
+    for name, b in blocks:
+        if not b:
+            continue
+        if state == "first hop" and cnt(b, "ds_read_u8"):
+            state = "steps"
+        kind = state
+        if cnt(b, "v_rcp_f32"):
+            kind = "modulo path"
+        elif state == "steps" and cnt(b, "ds_read_u16") >= 4:
+            kind = "jump round"
+            rounds.append(cnt(b, "v_"))
+        elif state == "steps" and cnt(b, "global_store"):
+            kind = "U store"
+        v, sa, d = cnt(b, "v_"), cnt(b, "s_"), cnt(b, "ds_")
+        t = tot.setdefault(kind, [0, 0, 0, 0])
+        for i, q in enumerate((v, sa, d, cnt(b, "v_ffbh"))):
+            t[i] += q
+        if v + d > 3:
+            print(f"  {name:12s} {kind:12s} VALU {v:4d}  SALU {sa:4d}  DS {d:3d}  ffbh {cnt(b, 'v_ffbh')}"
+                  f"  ds_write_b64 {cnt(b, 'ds_write_b64')}  barriers {cnt(b, 's_barrier')}")
+    for k, t in tot.items():
+        print(f"{k:12s} VALU {t[0]:4d}  SALU {t[1]:4d}  DS {t[2]:3d}  ffbh {t[3]}")
+    if rounds:
+        print("jump rounds:", " ".join(map(str, rounds)), "VALU each")
+
+
 def main():
+    if "--resolve" in sys.argv[1:]:
+        text = isa([a for a in sys.argv[1:] if a != "--resolve"])
+        return resolve(kernel(text, "_ZN2dq12_GLOBAL__N_120inflate_block_kernelILb0"))
     text = isa(sys.argv[1:])
     ker = kernel(text, "_ZN2dq12_GLOBAL__N_120inflate_block_kernelILb0")
     seen = {}

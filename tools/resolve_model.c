@@ -11,7 +11,13 @@
 //     the same bytes dist earlier);
 //   - rounds needed when the output is cut into ordered steps of S bytes (a match whose redirected
 //     source lies before its step's start is final at its step).
+//   - --nibbles: the start bits of every aligned group of four output bytes (a thread's group in
+//     the kernel's resolve: at most two matches own its bytes);
+//   - --pending: bytes still pending after the first hop (a copy whose source lies in the byte's
+//     own 512-byte step), per wave of 64 lanes holding one byte (64 bytes) or four contiguous
+//     bytes (256 bytes: the first and second half of a step) per lane.
 // Development tool (not built by the product, not a test): cc -O2 -o /tmp/rm tools/resolve_model.c
+//   /tmp/rm file.bam [maxblocks] [--nibbles] [--pending]
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -144,11 +150,14 @@ typedef struct {
   long rjumps;
   long hops_lit, hops_lit_max, hops_win[8], win_rounds[8];
   long dag_steps, dag_need_prev, dag_depth_sum, dag_depth_max, dag_need_prev2;
+  long nib[16], groups;
+  // [0] one byte per lane, [1] four per lane first half of a step, [2] second half
+  long pw_waves[3], pw_bytes[3], pw_lanes[3], pw_empty[3], pend_bytes;
 } Stats;
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s file.bam [maxblocks]\n", argv[0]);
+    fprintf(stderr, "usage: %s file.bam [maxblocks] [--nibbles] [--pending]\n", argv[0]);
     return 2;
   }
   FILE *f = fopen(argv[1], "rb");
@@ -159,7 +168,13 @@ int main(int argc, char **argv) {
   uint8_t *buf = malloc((size_t)fl + 16);
   if (fread(buf, 1, (size_t)fl, f) != (size_t)fl) return 2;
   fclose(f);
-  long maxb = argc > 2 ? atol(argv[2]) : 1L << 40;
+  long maxb = 1L << 40;
+  int opt_nib = 0, opt_pend = 0;
+  for (int i = 2; i < argc; i++) {
+    if (!strcmp(argv[i], "--nibbles")) opt_nib = 1;
+    else if (!strcmp(argv[i], "--pending")) opt_pend = 1;
+    else maxb = atol(argv[i]);
+  }
   Stats S;
   memset(&S, 0, sizeof S);
   Tok *tk = malloc(sizeof(Tok) * 70000);
@@ -300,6 +315,41 @@ int main(int argc, char **argv) {
         S.hops_win[wi] += hw;
       }
     }
+    {  // groups of four bytes: start bits; pending bytes after the first hop, per wave
+      static uint8_t st[70004], pend[70004];
+      memset(st, 0, sizeof st);
+      memset(pend, 0, sizeof pend);
+      for (int i = 0; i < nt; i++)
+        if (tk[i].len) st[tk[i].pos] = 1;
+      for (int x = 0; x < ol; x++) {
+        pend[x] = src1[x] != x && src1[x] >= (x & ~511);
+        S.pend_bytes += pend[x];
+      }
+      for (int g = 0; g < ol; g += 4) {
+        S.nib[st[g] | st[g + 1] << 1 | st[g + 2] << 2 | st[g + 3] << 3]++;
+        S.groups++;
+      }
+      for (int w0 = 0; w0 < ol; w0 += 64) {  // one byte per lane
+        int n = 0;
+        for (int x = w0; x < w0 + 64; x++) n += pend[x];
+        S.pw_waves[0]++;
+        S.pw_bytes[0] += n;
+        S.pw_lanes[0] += n;
+        S.pw_empty[0] += n == 0;
+      }
+      for (int w0 = 0; w0 < ol; w0 += 256) {  // four contiguous bytes per lane
+        int k = 1 + ((w0 >> 8) & 1), n = 0, ln = 0;
+        for (int x = w0; x < w0 + 256; x += 4) {
+          int c = pend[x] + pend[x + 1] + pend[x + 2] + pend[x + 3];
+          n += c;
+          ln += c != 0;
+        }
+        S.pw_waves[k]++;
+        S.pw_bytes[k] += n;
+        S.pw_lanes[k] += ln;
+        S.pw_empty[k] += n == 0;
+      }
+    }
     {  // step DAG (512-byte steps): final source of each byte after in-step resolution
       static int32_t fin[70000], sd[200];
       int ns = (ol + 511) / 512;
@@ -368,6 +418,32 @@ int main(int argc, char **argv) {
     }
   }
   double B = (double)S.blocks;
+  if (opt_nib) {
+    printf("groups of four output bytes: %ld in %ld blocks; start bits (bit i: a match starts at byte i):\n",
+           S.groups, S.blocks);
+    long one = 0, two = 0;
+    for (int i = 0; i < 16; i++) {
+      if (S.nib[i]) printf("  nibble %2d: %9ld  %5.1f %%\n", i, S.nib[i], 100.0 * S.nib[i] / S.groups);
+      int pc = (i & 1) + (i >> 1 & 1) + (i >> 2 & 1) + (i >> 3 & 1);
+      if (pc == 1) one += S.nib[i];
+      if (pc > 1) two += S.nib[i];
+    }
+    printf("  no start %.1f %%, one start %.1f %%, two or more %.1f %%\n", 100.0 * S.nib[0] / S.groups,
+           100.0 * one / S.groups, 100.0 * two / S.groups);
+  }
+  if (opt_pend) {
+    static const char *nm[3] = {"1 byte per lane (64 bytes)", "4 bytes per lane, first half of a step",
+                                "4 bytes per lane, second half of a step"};
+    printf("pending after the first hop (source in the byte's own 512-byte step): %.1f %% of all bytes\n",
+           100.0 * S.pend_bytes / S.bytes);
+    for (int k = 0; k < 3; k++)
+      printf("  %-40s waves %8ld  pending bytes per wave %6.1f  lanes with a pending byte %5.1f of 64 (%.1f %%)  waves with none %.1f %%\n",
+             nm[k], S.pw_waves[k], (double)S.pw_bytes[k] / S.pw_waves[k], (double)S.pw_lanes[k] / S.pw_waves[k],
+             100.0 * S.pw_lanes[k] / (64.0 * S.pw_waves[k]), 100.0 * S.pw_empty[k] / S.pw_waves[k]);
+    printf("  4 bytes per lane, all waves: lanes with a pending byte %.1f %%\n",
+           100.0 * (S.pw_lanes[1] + S.pw_lanes[2]) / (64.0 * (S.pw_waves[1] + S.pw_waves[2])));
+  }
+  if (opt_nib || opt_pend) return 0;
   printf("blocks %ld  bytes/block %.0f  tokens/block %.0f  literals/block %.0f  matches/block %.0f\n",
          S.blocks, S.bytes / B, S.toks / B, S.lits / B, S.matches / B);
   printf("bytes in matches %.1f %%  mean match length %.2f  overlapping (dist < len) %.2f %%  dist < 16 %.2f %%\n",
