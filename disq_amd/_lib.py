@@ -114,7 +114,8 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_bgzf_compress", "dq_bgzf_compress_resident", "dq_bgzf_fetch",
            "dq_text_set_index", "dq_text_set_intervals", "dq_decode_file_multi",
            "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai",
-           "dq_text_write_tbi")
+           "dq_text_write_tbi", "dq_sam_open_memory", "dq_sam_open_path", "dq_sam_run",
+           "dq_sam_read")
 
 _lib = None
 _lock = threading.Lock()
@@ -185,6 +186,10 @@ def lib():
         L.dq_text_set_intervals.argtypes = [vp, P(C.c_char_p), P(C.c_int32), P(C.c_int32),
                                             C.c_int64]
         L.dq_text_write_tbi.argtypes = [vp, P(P(C.c_uint8)), P(C.c_int64), P(C.c_double)]
+        L.dq_sam_open_memory.argtypes = [vp, vp, C.c_int64]
+        L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
+        L.dq_sam_run.argtypes = [vp, P(DqStats)]
+        L.dq_sam_read.argtypes = [vp, C.c_int32, P(P(DqBatch))]
         L.dq_bgzf_compress.argtypes = [vp, vp, C.c_int64, P(C.c_void_p), P(C.c_int64)]
         L.dq_bgzf_compress_resident.argtypes = [vp, P(C.c_int64), P(C.c_double)]
         L.dq_bgzf_fetch.argtypes = [vp, vp, C.c_int64]
@@ -523,6 +528,31 @@ class Context:
         self.tbi_ms = ms.value
         return out
 
+    # ---- SAM text path
+    def sam_open_bytes(self, data):
+        """An uncompressed SAM text (dq_sam_open_memory); header() then returns the BAM header
+        built from its leading '@' lines."""
+        buf = np.frombuffer(data, np.uint8)
+        check(self._h, lib().dq_sam_open_memory(self._h, buf.ctypes.data if len(buf) else None,
+                                                len(buf)))
+
+    def sam_open_path(self, path):
+        check(self._h, lib().dq_sam_open_path(self._h, os.fsencode(path)))
+
+    def sam_run(self):
+        """Lines -> BAM records, hashes and per-split digests, left in HBM (dq_sam_run)."""
+        st = DqStats()
+        check(self._h, lib().dq_sam_run(self._h, C.byref(st)))
+        return st
+
+    def sam_read(self, with_raw=True):
+        """Every split's records as a batch like read()'s (dq_sam_read): raw = BAM record bytes,
+        voffset = the offset of each line's first byte in the file."""
+        self._arena_guard("sam_read")
+        bp = C.POINTER(DqBatch)()
+        check(self._h, lib().dq_sam_read(self._h, export_mode(with_raw), C.byref(bp)))
+        return batch_to_numpy(bp, self)
+
     def set_index(self, bai_bytes):
         if bai_bytes is None:
             check(self._h, lib().dq_set_index(self._h, None, 0))
@@ -659,7 +689,7 @@ CHECK_SITES = ("K1 candidate slot", "K2 bit reader word", "K2 image store", "K2 
                "K2 per-lane arrays", "K2 match bitmap", "K2 resolve next pointer",
                "K2 resolve source", "K3 record staging", "K2 last_start",
                "deflate bucket-list slot", "deflate staged symbol", "deflate image word",
-               "K3 segment speculation", ".bai table slot", ".tbi table slot")
+               "K3 segment speculation", ".bai table slot", ".tbi / SAM table slot")
 
 
 def checked_report():

@@ -19,22 +19,51 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <sys/mman.h>
 #include <mutex>
 #include <vector>
 
 #include "../../include/disq_gpu.h"
 #include "dq_internal.h"
+#include "dq_sam_core.h"
 
 using namespace dq;
 
 namespace {
 
+// Owns one device allocation.  Not copyable: a copy would free the buffer twice (and a swap made
+// of copies frees a live one); moves and swap() hand the allocation over.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      if (p) (void)hipFree(p);
+      p = o.p;
+      cap = o.cap;
+      o.p = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
   ~DevBuf() {
     if (p) (void)hipFree(p);
+  }
+  void swap(DevBuf& o) noexcept {
+    void* tp = p;
+    p = o.p;
+    o.p = tp;
+    const size_t tc = cap;
+    cap = o.cap;
+    o.cap = tc;
   }
   template <typename T>
   T* as() const {
@@ -51,6 +80,9 @@ struct DevBuf {
     return e;
   }
 };
+
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
+              "a copied DevBuf frees its buffer twice");
 
 struct Interval {
   int32_t ref, start, end;
@@ -119,6 +151,15 @@ struct dq_ctx {
   std::vector<int32_t> tiv_cid, tiv_start, tiv_end;  // per interval (contig id into tiv_contig)
   DevBuf t_ivnames, t_ivnoff, t_ivbeg, t_ivstart, t_ivend, t_ivmaxend;
   int64_t t_pruned = 0;                          // splits the index filter removed
+  // SAM text path (dq_sam_*): C holds the text itself; the records are encoded into sam_rec (their
+  // offsets in rec_lin, rows in the f_* arrays), the built BAM header is hdr.  The line scan shares
+  // the text path's terminator and keep / scan buffers (a context is in one mode at a time).
+  bool sam_mode = false;
+  bool have_sam = false;
+  int32_t sam_bom = 0;              // the text starts with a UTF-8 BOM
+  unsigned long long sam_init[4] = {~0ull, 0, 0, 0};  // first failing line | undecided | fix-ups
+  DevBuf s_ls, s_vs, s_vl, s_splits, s_status, s_size, s_fix, s_refs, sam_rec;
+  dq::SamRefs sam_refs{};
   // BGZF deflate (write path)
   DevBuf z_in, z_stage, z_link, z_slots, z_size, z_off, z_out;
   int64_t z_len = 0;
@@ -140,6 +181,9 @@ struct dq_ctx {
   DevBuf x_bs4, x_boff, x_voff, x_parts;  // batch export: raw offsets, voffsets, digests
   int64_t h2d_bytes = 0;            // compressed bytes copied host -> device by the last open
   const uint8_t* cbuf() const { return cext ? cext : C.as<uint8_t>(); }
+  // where the records' bytes lie (record i at rec_lin[i]): the inflated stream, or the SAM path's
+  // encoded records
+  const uint8_t* rec_src() const { return sam_mode ? sam_rec.as<uint8_t>() : U.as<uint8_t>(); }
   // kernel 1
   DevBuf slots, counts, offs, cand, flags, voff, scal, tmp;
   DevBuf scan_over, scan_map, scan_big;  // second scan pass (dense BGZF regions)
@@ -564,6 +608,7 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
 
 // ------------------------------------------------------------------ pipeline
 static int run_pipeline(dq_ctx* ctx) {
+  if (ctx->sam_mode) RET(DQ_EINVAL, "a SAM context (dq_sam_open_*) takes the dq_sam_* calls only");
   if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
   if (ctx->have_pipeline) return 0;
   ctx->span_parts_valid = false;
@@ -1035,27 +1080,27 @@ static int run_pipeline(dq_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ BGZF text (VCF) path
-// The terminator list of the resident stream: ctx->t_term[0, ctx->t_nterm), ascending.
-static int text_terms(dq_ctx* ctx) {
+// The terminator list of the ulen bytes at U (device; 256 readable zero bytes past them, which
+// term_mask's 33-byte loads rely on): ctx->t_term[0, ctx->t_nterm), ascending.
+static int text_terms_at(dq_ctx* ctx, const uint8_t* U, int64_t ulen) {
   hipStream_t s = ctx->s;
-  const int64_t ulen = ctx->ulen;
   int rc;
   const int64_t nt = text_tiles(ulen);
   if ((rc = ensure_all(ctx, ctx->t_tcount, 4 * (size_t)std::max<int64_t>(1, nt)))) return rc;
   if ((rc = ensure_all(ctx, ctx->t_toff, 8 * (size_t)(nt + 1)))) return rc;
   if ((rc = ensure_all(ctx, ctx->tmp, sizeof(int64_t) * (size_t)(4 * (nt / 1024 + 1) + 4096)))) return rc;
-  launch_text_terms(ctx->U.as<uint8_t>(), ulen, ctx->t_tcount.as<int32_t>(), nullptr, nullptr, false, s);
+  launch_text_terms(U, ulen, ctx->t_tcount.as<int32_t>(), nullptr, nullptr, false, s);
   if (nt > 0)
     launch_exclusive_scan_i32(ctx->t_tcount.as<int32_t>(), ctx->t_toff.as<int64_t>(), nt,
                               ctx->tmp.as<int64_t>(), s);
   int64_t nterm = 0;
   if (nt > 0 && (rc = get_i64(ctx, ctx->t_toff.as<int64_t>() + nt, &nterm))) return rc;
   if ((rc = ensure_all(ctx, ctx->t_term, 8 * (size_t)(nterm + 1)))) return rc;
-  launch_text_terms(ctx->U.as<uint8_t>(), ulen, nullptr, ctx->t_toff.as<int64_t>(),
-                    ctx->t_term.as<int64_t>(), true, s);
+  launch_text_terms(U, ulen, nullptr, ctx->t_toff.as<int64_t>(), ctx->t_term.as<int64_t>(), true, s);
   ctx->t_nterm = nterm;
   return 0;
 }
+static int text_terms(dq_ctx* ctx) { return text_terms_at(ctx, ctx->U.as<uint8_t>(), ctx->ulen); }
 
 // TextInputFormat + LineRecordReader over Disq's splittable BGZF codec, per split (dq_text.hip
 // holds the characterisation, oracle/disq_oracle.c the literal restatement): terminators of the
@@ -1619,10 +1664,10 @@ static int make_batch(dq_ctx* ctx, const std::vector<std::pair<int64_t, int64_t>
     if (direct) {  // consecutive chain records are contiguous in U
       int64_t lo = 0;
       XCHK(hipMemcpy(&lo, ctx->rec_lin.as<int64_t>() + first, 8, hipMemcpyDeviceToHost));
-      if ((rc = raw_d2h(ctx->U.as<uint8_t>() + lo))) return fail(rc);
+      if ((rc = raw_d2h(ctx->rec_src() + lo))) return fail(rc);
     } else {
       if ((rc = ensure_all(ctx, ctx->x_raw, (size_t)raw_len))) return fail(rc);
-      launch_gather_raw(ctx->U.as<uint8_t>(), ctx->rec_lin.as<int64_t>(), ctx->f_bs.as<int32_t>(),
+      launch_gather_raw(ctx->rec_src(), ctx->rec_lin.as<int64_t>(), ctx->f_bs.as<int32_t>(),
                         d_idx, 0, n, ctx->x_boff.as<int64_t>(), ctx->x_raw.as<uint8_t>(), s);
       if (split) {  // the second stream waits for the gather too
         XCHK(hipEventRecord(ctx->ev_x[0], s));
@@ -2065,6 +2110,206 @@ static int run_span(dq_ctx* ctx, const dq_traversal* tr, dq_stats* out) {
   }
 }
 
+// ------------------------------------------------------------------ SAM text path (row f7)
+// SamSource.getReads over the resident text (ctx->cbuf(), flen bytes and the opens' zero pad; nothing
+// is put in U): terminators, line table, partitions, size pass + scan, encode pass, float fix-ups,
+// hashes and digests (dq_sam.hip).  Everything stays in HBM.
+static int sam_run(dq_ctx* ctx) {
+  if (!ctx->sam_mode) RET(DQ_EINVAL, "not a SAM context (dq_sam_open_*)");
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  if (ctx->have_sam) return 0;
+  hipStream_t s = ctx->s;
+  const int64_t L = ctx->flen;
+  const uint8_t* T = ctx->cbuf();
+  int rc;
+  if ((rc = ensure_all(ctx, ctx->scal, 4096))) return rc;
+  unsigned long long* d_scal = ctx->scal.as<unsigned long long>() + 16;
+  HIPCHK(hipEventRecord(ctx->ev[0], s));
+  // ---- terminators and the line table
+  if ((rc = text_terms_at(ctx, T, L))) return rc;
+  const int64_t nterm = ctx->t_nterm;
+  HIPCHK(hipEventRecord(ctx->ev[2], s));
+  int64_t last = -1;
+  if (nterm > 0 && (rc = get_i64(ctx, ctx->t_term.as<int64_t>() + (nterm - 1), &last))) return rc;
+  int64_t nl = nterm + ((nterm == 0 ? L > 0 : last + 1 < L) ? 1 : 0);
+  if (ctx->sam_bom && L == 3) nl = 0;  // a line of only the BOM and no terminator is no record
+  const size_t nl1 = (size_t)std::max<int64_t>(1, nl);
+  if ((rc = ensure_all(ctx, ctx->s_ls, 8 * nl1)) || (rc = ensure_all(ctx, ctx->s_vs, 8 * nl1)) ||
+      (rc = ensure_all(ctx, ctx->s_vl, 4 * nl1)) || (rc = ensure_all(ctx, ctx->t_keep, nl1)) ||
+      (rc = ensure_all(ctx, ctx->t_keep32, 4 * nl1)) || (rc = ensure_all(ctx, ctx->t_koff, 8 * (nl1 + 1))) ||
+      (rc = ensure_all(ctx, ctx->t_kept, 8 * nl1)) || (rc = ensure_scan(ctx, nl)))
+    return rc;
+  launch_sam_lines(T, L, ctx->t_term.as<int64_t>(), nterm, nl, ctx->sam_bom, ctx->s_ls.as<int64_t>(),
+                   ctx->s_vs.as<int64_t>(), ctx->s_vl.as<int32_t>(), ctx->t_keep.as<uint8_t>(), s);
+  launch_keep_to_i32(ctx->t_keep.as<uint8_t>(), nl, ctx->t_keep32.as<int32_t>(), s);
+  int64_t n = 0;
+  if (nl > 0) {
+    launch_exclusive_scan_i32(ctx->t_keep32.as<int32_t>(), ctx->t_koff.as<int64_t>(), nl,
+                              ctx->tmp.as<int64_t>(), s);
+    if ((rc = get_i64(ctx, ctx->t_koff.as<int64_t>() + nl, &n))) return rc;
+    if (n < 0 || n > nl) RET(DQ_EDEVICE, "SAM line scan: bad kept count");
+  }
+  launch_compact_kept(nullptr, ctx->t_keep.as<uint8_t>(), ctx->t_koff.as<int64_t>(), nl,
+                      ctx->t_kept.as<int64_t>(), s);
+  // ---- partitions: the FileInputFormat splits, the same arithmetic as every other path (a1)
+  std::vector<std::pair<int64_t, int64_t>> splits;
+  if (path_splits(ctx->o, L, splits)) RET(DQ_EINVAL, "splitSize must be > 0 with useNio");
+  const int64_t nsplit = (int64_t)splits.size();
+  std::vector<int64_t> sp(2 * (size_t)nsplit + 2);
+  for (int64_t i = 0; i < nsplit; i++) {
+    sp[2 * (size_t)i] = splits[(size_t)i].first;
+    sp[2 * (size_t)i + 1] = splits[(size_t)i].second;
+  }
+  if ((rc = ensure_all(ctx, ctx->s_splits, 8 * sp.size())) ||
+      (rc = ensure_all(ctx, ctx->parts, sizeof(PartRange) * (size_t)(nsplit + 1))))
+    return rc;
+  HIPCHK(hipMemcpyAsync(ctx->s_splits.p, sp.data(), 8 * sp.size(), hipMemcpyHostToDevice, s));
+  launch_sam_parts(ctx->s_splits.as<int64_t>(), nsplit, ctx->s_ls.as<int64_t>(), nl,
+                   ctx->t_koff.as<int64_t>(), ctx->parts.as<PartRange>(), s);
+  HIPCHK(hipStreamSynchronize(s));  // sp is read by the copy
+  HIPCHK(hipEventRecord(ctx->ev[3], s));
+  // ---- size pass, the first failing line, the records' offsets
+  const size_t n1 = (size_t)std::max<int64_t>(1, n);
+  if ((rc = ensure_all(ctx, ctx->s_status, 4 * n1)) || (rc = ensure_all(ctx, ctx->s_size, 4 * n1)) ||
+      (rc = ensure_all(ctx, ctx->rec_lin, 8 * (n1 + 1))) || (rc = ensure_scan(ctx, n)))
+    return rc;
+  ctx->sam_init[0] = ~0ull;
+  ctx->sam_init[1] = ctx->sam_init[2] = ctx->sam_init[3] = 0;
+  HIPCHK(hipMemcpyAsync(d_scal, ctx->sam_init, sizeof ctx->sam_init, hipMemcpyHostToDevice, s));
+  launch_sam_sizes(T, ctx->s_vs.as<int64_t>(), ctx->s_vl.as<int32_t>(), nl, ctx->t_kept.as<int64_t>(), n,
+                   ctx->sam_refs, ctx->s_status.as<int32_t>(), ctx->s_size.as<int32_t>(), d_scal, s);
+  unsigned long long sc[2] = {~0ull, 0};
+  int64_t total = 0;
+  if (n > 0) {
+    launch_exclusive_scan_i32(ctx->s_size.as<int32_t>(), ctx->rec_lin.as<int64_t>(), n,
+                              ctx->tmp.as<int64_t>(), s);
+    HIPCHK(hipMemcpyAsync(sc, d_scal, sizeof sc, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&total, ctx->rec_lin.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  if (sc[0] != ~0ull) {
+    const int64_t j = (int64_t)sc[0];
+    if (j < 0 || j >= n) RET(DQ_EDEVICE, "SAM size pass: bad failing-line index");
+    int32_t st = 0;
+    int64_t k = 0;
+    HIPCHK(hipMemcpy(&st, ctx->s_status.as<int32_t>() + j, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&k, ctx->t_kept.as<int64_t>() + j, 8, hipMemcpyDeviceToHost));
+    char nb[8];
+    RET(DQ_EFORMAT, "SAM line " + std::to_string(k) + ": " + dqs::sam_status_name(st, nb));
+  }
+  const int64_t nund = (int64_t)sc[1];
+  if (total < 36 * n) RET(DQ_EDEVICE, "SAM size pass: bad record bytes total");
+  // ---- encode pass: records back to back in line order (slack for the hash pass's word loads)
+  if ((rc = ensure_all(ctx, ctx->sam_rec, (size_t)total + 64)) ||
+      (rc = ensure_all(ctx, ctx->s_fix, 24 * (size_t)std::max<int64_t>(1, nund))))
+    return rc;
+  {
+    DevBuf* b8[] = {&ctx->f_voff, &ctx->f_hash};
+    DevBuf* b4[] = {&ctx->f_bs, &ctx->f_ref, &ctx->f_pos, &ctx->f_lseq, &ctx->f_nref, &ctx->f_npos,
+                    &ctx->f_tlen};
+    DevBuf* b2[] = {&ctx->f_flag, &ctx->f_bin, &ctx->f_ncig};
+    DevBuf* b1[] = {&ctx->f_mapq, &ctx->f_lrn};
+    for (auto* b : b8) if ((rc = ensure_all(ctx, *b, 8 * n1))) return rc;
+    for (auto* b : b4) if ((rc = ensure_all(ctx, *b, 4 * n1))) return rc;
+    for (auto* b : b2) if ((rc = ensure_all(ctx, *b, 2 * n1))) return rc;
+    for (auto* b : b1) if ((rc = ensure_all(ctx, *b, n1))) return rc;
+  }
+  launch_sam_encode(T, ctx->s_ls.as<int64_t>(), ctx->s_vs.as<int64_t>(), ctx->s_vl.as<int32_t>(), nl,
+                    ctx->t_kept.as<int64_t>(), n, ctx->sam_refs, ctx->rec_lin.as<int64_t>(),
+                    ctx->s_size.as<int32_t>(), ctx->sam_rec.as<uint8_t>(), ctx->soa(),
+                    ctx->s_fix.as<int64_t>(), nund, d_scal + 2, s);
+  // ---- float fix-ups: the texts sam_parse_float left undecided, converted by strtof (normally none)
+  if (nund > 0) {
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((int64_t)cnt != nund) RET(DQ_EDEVICE, "SAM encode pass: the fix-up count differs from the size pass's");
+    std::vector<int64_t> ent(3 * (size_t)nund);
+    HIPCHK(hipMemcpy(ent.data(), ctx->s_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
+    std::string txt;
+    for (int64_t e = 0; e < nund; e++) {
+      const int64_t oo = ent[3 * (size_t)e], ta = ent[3 * (size_t)e + 1], tn = ent[3 * (size_t)e + 2];
+      if (oo < 0 || oo + 4 > total || ta < 0 || tn <= 0 || ta + tn > L)
+        RET(DQ_EDEVICE, "SAM encode pass: bad fix-up entry");
+      txt.assign((size_t)tn, '\0');
+      HIPCHK(hipMemcpy(&txt[0], T + ta, (size_t)tn, hipMemcpyDeviceToHost));
+      const float f = strtof(txt.c_str(), nullptr);
+      HIPCHK(hipMemcpy(ctx->sam_rec.as<uint8_t>() + oo, &f, 4, hipMemcpyHostToDevice));
+    }
+  }
+  // ---- hashes (the BAM path's hash of a record's 4 + block_size bytes) and partition digests
+  launch_span_hash(ctx->sam_rec.as<uint8_t>(), ctx->rec_lin.as<int64_t>(), ctx->s_size.as<int32_t>(), n,
+                   ctx->f_hash.as<uint64_t>(), s);
+  launch_partition_digest2(ctx->f_hash.as<uint64_t>(), ctx->parts.as<PartRange>(), nsplit, s);
+  HIPCHK(hipEventRecord(ctx->ev[4], s));
+  ctx->parts_h.assign((size_t)nsplit, PartRange{});
+  HIPCHK(hipMemcpyAsync(ctx->parts_h.data(), ctx->parts.p, sizeof(PartRange) * (size_t)nsplit,
+                        hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dq_stats& S = ctx->stats;
+  S = dq_stats{};
+  S.compressed_bytes = S.decompressed_bytes = L;
+  S.n_blocks = 0;
+  S.n_partitions = nsplit;
+  int64_t emitted = 0;
+  uint64_t dg = 0;
+  for (int64_t i = 0; i < nsplit; i++) {
+    const PartRange& r = ctx->parts_h[(size_t)i];
+    if (r.begin < 0 || r.end < r.begin || r.end > n) RET(DQ_EDEVICE, "SAM partitions: bad record range");
+    emitted += r.end - r.begin;
+    dg += dq_mix64(r.digest ^ ((uint64_t)(i + 1) * DQ_K_WORD));
+  }
+  if (emitted != n) RET(DQ_EDEVICE, "SAM partitions: the kept lines are not covered exactly once");
+  S.n_records = n;
+  S.n_filtered = nl - n;  // '@' lines dropped
+  S.digest = dg;
+  S.ms_plan = ev_ms(ctx->ev[2], ctx->ev[3]);
+  S.ms_records = ev_ms(ctx->ev[3], ctx->ev[4]);
+  S.ms_total = ev_ms(ctx->ev[0], ctx->ev[4]);
+  S.h2d_bytes = ctx->h2d_bytes;
+  S.owned_bytes = L;
+  ctx->nrec = n;
+  ctx->voff_h.clear();
+  ctx->have_sam = true;
+  return 0;
+}
+
+// The header of a SAM text from its first bytes (whole: they are the whole file): ctx->hdr = the BAM
+// header, the reference names and lengths, and the device name table.  Returns 1 when the prefix is
+// too short.
+static int sam_set_header(dq_ctx* ctx, const uint8_t* t, int64_t n, bool whole) {
+  dqs::SamHeader H;
+  const int r = dqs::sam_header_build(t, n, whole, &H);
+  if (r == 1) return 1;
+  if (r) RET(DQ_EFORMAT, "SAM header: an @SQ line without SN or a valid LN");
+  ctx->hdr = H.bam;
+  ctx->header_bytes = (int64_t)H.bam.size();
+  ctx->n_ref = (int32_t)H.names.size();
+  ctx->ref_name = H.names;
+  ctx->ref_len = H.lens;
+  ctx->sam_bom = n >= 3 && t[0] == 0xEF && t[1] == 0xBB && t[2] == 0xBF;
+  dqs::RefTableHost R;
+  dqs::sam_ref_table_build(H.names, &R);
+  // one buffer: hashes | name offsets | indices | name bytes
+  const size_t nr = H.names.size();
+  const size_t o_hash = 0, o_off = o_hash + 8 * nr, o_idx = o_off + 4 * (nr + 1),
+               o_names = o_idx + 4 * nr, bytes = o_names + R.names.size();
+  std::vector<uint8_t> buf(bytes + 8);
+  if (nr) {
+    memcpy(&buf[o_hash], R.hash.data(), 8 * nr);
+    memcpy(&buf[o_idx], R.idx.data(), 4 * nr);
+  }
+  memcpy(&buf[o_off], R.name_off.data(), 4 * (nr + 1));
+  memcpy(&buf[o_names], R.names.data(), R.names.size());
+  int rc;
+  if ((rc = ensure_all(ctx, ctx->s_refs, buf.size()))) return rc;
+  HIPCHK(hipMemcpy(ctx->s_refs.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  const uint8_t* d = ctx->s_refs.as<uint8_t>();
+  ctx->sam_refs = SamRefs{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
+                          (const int32_t*)(d + o_off), d + o_names, (int32_t)nr};
+  return 0;
+}
+
 // ------------------------------------------------------------------ opening inputs
 static void reset_open(dq_ctx* ctx, int64_t len) {
   ctx->plan_cached = false;
@@ -2080,6 +2325,8 @@ static void reset_open(dq_ctx* ctx, int64_t len) {
   ctx->chunk_mode = false;
   ctx->text_mode = false;
   ctx->have_text = false;
+  ctx->sam_mode = false;
+  ctx->have_sam = false;
 }
 
 // Bytes [off, off + len) of an open file into C (plus the 4 KiB zero pad): read() into two pinned
@@ -2617,7 +2864,7 @@ int dq_get_stats(dq_ctx* ctx, dq_stats* stats) {
 int dq_partition_digests(dq_ctx* ctx, int64_t* counts, uint64_t* digests, int64_t cap,
                          int64_t* n) {
   if (!ctx || !n) return DQ_EINVAL;
-  if (!ctx->have_pipeline && !ctx->span_parts_valid)
+  if (!ctx->have_pipeline && !ctx->span_parts_valid && !ctx->have_sam)
     RET(DQ_EINVAL, "no pipeline run (call dq_run_resident first)");
   *n = (int64_t)ctx->parts_h.size();
   for (int64_t i = 0; i < std::min(cap, *n); i++) {
@@ -3044,6 +3291,16 @@ int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
 int dq_read_header(dq_ctx* ctx, dq_header_info* info, uint8_t* header_bytes, int64_t cap) {
   if (!ctx) return DQ_EINVAL;
   ON_DEVICE(ctx);
+  if (ctx->sam_mode) {  // the BAM header built from the '@' lines at the open; no record pointers
+    if (info) {
+      info->n_ref = ctx->n_ref;
+      info->header_bytes = ctx->header_bytes;
+      info->first_record_voffset = 0;
+    }
+    if (header_bytes && cap > 0)
+      memcpy(header_bytes, ctx->hdr.data(), (size_t)std::min<int64_t>(cap, ctx->header_bytes));
+    return 0;
+  }
   int rc = run_pipeline(ctx);
   if (rc) return rc;
   if (info) {
@@ -3335,6 +3592,76 @@ int dq_text_open_path(dq_ctx* ctx, const char* path) {
   int rc = dq_open_path(ctx, path);
   if (rc == 0) ctx->text_mode = true;
   return rc;
+}
+
+// ---- SAM text (row f7).  The opens upload the text into C with the 4 KiB zero pad every open
+// writes after flen (dq_open_memory, upload_file_range), which the terminator scan's 33-byte loads
+// need; the '@' lines are parsed on the host into the BAM header dq_read_header returns.
+int dq_sam_open_memory(dq_ctx* ctx, const uint8_t* text, int64_t len) {
+  int rc = dq_open_memory(ctx, text, len);
+  if (rc) return rc;
+  if ((rc = sam_set_header(ctx, text, len, true))) {
+    ctx->have_file = false;
+    return rc;
+  }
+  ctx->sam_mode = true;
+  return 0;
+}
+
+int dq_sam_open_path(dq_ctx* ctx, const char* path) {
+  if (!ctx || !path) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  Fd f;
+  int64_t len = 0;
+  int rc = open_fd(ctx, path, f, &len);
+  if (rc) return rc;
+  if ((rc = upload_file_range(ctx, f.fd, 0, len))) return rc;
+  ctx->have_file = false;  // until the header is in
+  std::vector<uint8_t> pre;
+  for (int64_t n = std::min<int64_t>(len, 1 << 20);; n = std::min<int64_t>(len, n * 8)) {
+    pre.resize((size_t)n);
+    int64_t got = 0;
+    while (got < n) {
+      const ssize_t r = pread(f.fd, pre.data() + got, (size_t)(n - got), (off_t)got);
+      if (r <= 0) RET(DQ_EIO, "short read");
+      got += (int64_t)r;
+    }
+    rc = sam_set_header(ctx, pre.data(), n, n >= len);
+    if (rc != 1) break;
+  }
+  if (rc) return rc;
+  ctx->have_file = true;
+  ctx->sam_mode = true;
+  return 0;
+}
+
+int dq_sam_run(dq_ctx* ctx, dq_stats* stats) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  ctx->have_sam = false;  // a re-run times the whole pipeline again
+  int rc = sam_run(ctx);
+  if (rc) return rc;
+  if (stats) *stats = ctx->stats;
+  return 0;
+}
+
+int dq_sam_read(dq_ctx* ctx, int32_t with_raw, dq_batch** out) {
+  if (!ctx || !out) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  int rc = sam_run(ctx);
+  if (rc) return rc;
+  // every split is a partition, the empty ones too; consecutive partitions form one run of the
+  // record buffer, which make_batch copies straight out
+  std::vector<int64_t> bounds{0};
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  int64_t total = 0;
+  for (const PartRange& r : ctx->parts_h) {
+    ranges.push_back({r.begin, r.end});
+    total += r.end - r.begin;
+    bounds.push_back(total);
+  }
+  return make_batch(ctx, ranges, nullptr, with_raw, bounds, out);
 }
 
 int dq_text_run(dq_ctx* ctx, int32_t drop_header_lines, dq_stats* stats) {
@@ -3761,6 +4088,16 @@ int dq_checked_report(uint64_t words[4]) {
   words[0] = dq::dq_chk_take_kernels();
   words[1] = dq::dq_chk_take_inflate();
   words[2] = dq::dq_chk_take_text();
+  {  // the SAM unit shares the text word: counts added, excess by maximum, site bits OR-ed
+    const uint64_t a = words[2], b = dq::dq_chk_take_sam();
+    if (a == ~0ull || b == ~0ull) {
+      words[2] = ~0ull;
+    } else {
+      const uint64_t cnt = std::min<uint64_t>(0xffffffffull, (a >> 32) + (b >> 32));
+      const uint64_t ex = std::max((a >> 16) & 0xffff, (b >> 16) & 0xffff);
+      words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
+    }
+  }
   words[3] = dq::dq_chk_take_deflate();
 #ifdef DQ_CHECKED
   return 1;

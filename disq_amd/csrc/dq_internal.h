@@ -45,6 +45,7 @@ enum : int {
   CHK_K3_SPEC = 13,  // K3: the LDS-filtered segment speculation differs from seg_spec_kernel<64>
   CHK_BAI = 14,      // .bai build: a linear window, perm slot, chunk or bin outside its table
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
+  CHK_SAM = 15,      // SAM read (dq_sam.hip shares the bit): a line, size, record-byte or fix-up slot
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -387,7 +388,42 @@ void launch_tbi_runs(const uint8_t* U, int64_t ulen, const int64_t* term, int64_
 void launch_tbi_names(const uint8_t* U, const int64_t* nstart, const int32_t* nlen,
                       const int64_t* noff, int64_t nrun, int64_t nbytes, uint8_t* out, hipStream_t s);
 
+// Record hash of the n byte spans base[start[i], start[i] + len[i]): a thread
+// per span of up to 2048 bytes, a wave per longer one.  base: readable 16 bytes past every span.
+void launch_span_hash(const uint8_t* base, const int64_t* start, const int32_t* len, int64_t n,
+                      uint64_t* hash, hipStream_t s);
+
+// ------------------------------------------------------------------ SAM text path (dq_sam.hip)
+struct SamRefs {           // the @SQ names: hashes sorted ascending (ties by index), see dq_sam_core.h
+  const uint64_t* hash;
+  const int32_t* idx;
+  const int32_t* name_off;  // n + 1 offsets into names, by reference index
+  const uint8_t* names;
+  int32_t n;
+};
+// Lines of T[0, flen) from its terminator ends: value start and length (terminator excluded, a BOM
+// stripped from line 0 when bom), raw start, keep = the value does not start with '@'.
+void launch_sam_lines(const uint8_t* T, int64_t flen, const int64_t* term, int64_t nterm, int64_t nl,
+                      int32_t bom, int64_t* lstart, int64_t* vstart, int32_t* vlen, uint8_t* keep,
+                      hipStream_t s);
+// parts[i] = the kept-record range of split i: lines whose first byte s has start < s <= end
+// (offset 0 belongs to split 0); splits: nsplit (start, end) pairs; koff: exclusive scan of keep.
+void launch_sam_parts(const int64_t* splits, int64_t nsplit, const int64_t* lstart, int64_t nl,
+                      const int64_t* koff, PartRange* parts, hipStream_t s);
+// Size pass over the n kept lines (kept[j] = line index): status[j], size[j] = 4 + block_size;
+// scal[0] (all ones) takes the smallest failing j, scal[1] (zero) the undecided floats.
+void launch_sam_sizes(const uint8_t* T, const int64_t* vstart, const int32_t* vlen, int64_t nl,
+                      const int64_t* kept, int64_t n, SamRefs refs, int32_t* status, int32_t* size,
+                      unsigned long long* scal, hipStream_t s);
+// Encode pass: record j at rec[roff[j]], roff[n] = total bytes; SoA rows; undecided floats appended
+// to fix (3 words each: byte offset in rec, text offset in T, text length), counted in fix_cnt.
+void launch_sam_encode(const uint8_t* T, const int64_t* lstart, const int64_t* vstart,
+                       const int32_t* vlen, int64_t nl, const int64_t* kept, int64_t n, SamRefs refs,
+                       const int64_t* roff, const int32_t* size, uint8_t* rec, RecSoA soa,
+                       int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt, hipStream_t s);
+
 // DQ_CHECKED: each kernel unit's check words (count << 32 | site bits), read and reset
+uint64_t dq_chk_take_sam();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

@@ -325,6 +325,24 @@ __global__ __launch_bounds__(256) void text_long_hash_kernel(const uint8_t* __re
   }
 }
 
+// The same hash of n byte spans of a buffer (the SAM path's records): spans of up to TV_LONG bytes
+// here, a thread each; the longer ones by text_long_hash_kernel.
+__global__ __launch_bounds__(256) void span_hash_kernel(const uint8_t* __restrict__ base,
+                                                        const int64_t* __restrict__ start,
+                                                        const int32_t* __restrict__ slen, int64_t n,
+                                                        uint64_t* __restrict__ hash) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t len = slen[t];
+  if (len > TV_LONG) return;
+  const int64_t a = start[t];
+  const uint32_t* B32 = reinterpret_cast<const uint32_t*>(base);
+  uint64_t h = (uint64_t)len * DQ_K_LEN;
+  const int64_t nw = (len + 7) / 8;
+  for (int64_t w = 0; w < nw; w++) h += dq_mix64(tv_word(B32, a, len, w) ^ ((uint64_t)(w + 1) * DQ_K_WORD));
+  hash[t] = dq_mix64(h);
+}
+
 // Line values gathered into a compact byte buffer: one wave per line.
 __global__ __launch_bounds__(256) void text_gather_kernel(const uint8_t* __restrict__ U,
                                                           const int64_t* __restrict__ vstart,
@@ -813,6 +831,15 @@ void launch_text_terms(const uint8_t* U, int64_t ulen, int32_t* tile_count, cons
                        tile_count, tile_off, term_pos);
 }
 int64_t text_tiles(int64_t ulen) { return (ulen + TILE - 1) / TILE; }
+
+void launch_span_hash(const uint8_t* base, const int64_t* start, const int32_t* len, int64_t n,
+                      uint64_t* hash, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(span_hash_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, base, start,
+                     len, n, hash);
+  const unsigned g = (unsigned)std::min<int64_t>(2048, (n + 3) / 4);
+  hipLaunchKernelGGL(text_long_hash_kernel, dim3(g), dim3(256), 0, s, base, start, len, n, hash);
+}
 
 void launch_text_cr_fills(const uint8_t* U, const int64_t* uoff, const int32_t* blk_us, int64_t nblk,
                           int64_t* last_cr_fill, hipStream_t s) {

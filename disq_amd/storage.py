@@ -198,9 +198,12 @@ class HtsjdkReadsRddStorage:
         if not files:
             raise ValueError(f"No files found in {path}")
         first = files[0]
-        if not first.endswith(".bam"):
+        sam = first.endswith(".sam")  # SamFormat.fromPath: the first file's extension decides
+        if not sam and not first.endswith(".bam"):
             raise ValueError(f"Cannot find format extension for {path}")
         tp = traversalParameters
+        if sam and tp is not None:
+            raise ValueError("Traversal parameters are not supported for SAM text input")
         if tp is not None and tp.getIntervalsForTraversal() is None and \
                 not tp.getTraverseUnplacedUnmapped():
             # AbstractBinarySamSource.java:50-54
@@ -211,9 +214,12 @@ class HtsjdkReadsRddStorage:
             with _lib.Context(split_size=self._split_size, use_nio=self._use_nio,
                               verify_crc=self._verify_crc, device=self._device,
                               stringency=self._stringency) as ctx:
-                ctx.open_path(f)
+                if sam:
+                    ctx.sam_open_path(f)
+                else:
+                    ctx.open_path(f)
                 sbi = f + ".sbi"  # SBIIndex.FILE_EXTENSION, BamSource.java:69-72
-                if os.path.exists(sbi):
+                if not sam and os.path.exists(sbi):
                     with open(sbi, "rb") as fh:
                         ctx.set_splitting_index(fh.read(), self._use_sbi)
                 _, hraw = ctx.header()
@@ -240,7 +246,7 @@ class HtsjdkReadsRddStorage:
                                                  "sequence dictionary")
                             conv.append((idx, iv.getStart(), iv.getEnd()))
                     trav = (conv, tp.getTraverseUnplacedUnmapped())
-                b = ctx.read(with_raw=True, traversal=trav)
+                b = ctx.sam_read(with_raw=True) if sam else ctx.read(with_raw=True, traversal=trav)
                 po = b["part_offset"]
                 for p in range(len(po) - 1):
                     lo, hi = int(po[p]), int(po[p + 1])

@@ -24,6 +24,8 @@
  *                                                                           dq_read_header
  *   htsjdk BAMIndexer.createIndex / BinningIndexBuilder (the .bai that
  *     AbstractBinarySamSource.java:87-91 requires for an interval traversal)    dq_write_bai
+ *   SamSource.getReads, whole RDD of a SAM text file
+ *     (D/impl/formats/sam/SamSource.java:36-77)                             dq_sam_read
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -388,6 +390,34 @@ void dq_text_batch_free(dq_text_batch* b);
  * scan, inflate and the terminator scan. */
 int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms);
 
+/* ---- SAM text: SamSource.getReads -----------------------------
+ * An uncompressed SAM file read as Disq reads it (D/impl/formats/sam/SamSource.java:36-77): Hadoop
+ * TextInputFormat lines per split of PathSplitSource.getPathSplits (a line whose first byte is at s
+ * belongs to the split with start < s <= end, offset 0 to the first; LF, CR LF and a lone CR end a
+ * line; a UTF-8 BOM is dropped from the first value), '@' lines dropped wherever they stand, every
+ * other line through htsjdk SAMLineParser.parseLine and encoded as BAMRecordCodec encodes it.  The
+ * rules are DESIGN.md section 13.  After an open the context holds the BAM header built from the
+ * leading '@' lines (BAM\1, l_text, each line followed by LF, n_ref, per @SQ l_name, name, NUL, LN):
+ * dq_read_header returns it.  dq_sam_run leaves the records in HBM; stats: compressed_bytes =
+ * decompressed_bytes = the file's length, n_blocks = 0, n_records, n_partitions (every split is a
+ * partition, one in which no line starts an empty one), n_filtered = '@' lines dropped, digest as
+ * dq_text_run folds it, ms_plan / ms_records / ms_total; dq_get_stats and dq_partition_digests work
+ * after a run.  dq_sam_read returns an ordinary dq_batch (every export mode, the export arena,
+ * dq_batch_free): raw = the BAM records' bytes, hash = the hash the BAM path gives the same record,
+ * voffset = the offset of the line's first byte in the file (SAM text has no virtual offsets),
+ * part_offset / part_digest per split.  A malformed line gives DQ_EFORMAT and dq_last_error
+ * "SAM line <k>: <what>": k = the 0-based index of the first offending line in file order, counted
+ * over all lines; what = fields, QNAME, FLAG, RNAME, POS, MAPQ, CIGAR, RNEXT, PNEXT, TLEN, SEQ, QUAL
+ * or "tag XX".  A BAM or text call on a SAM context, and dq_sam_run / dq_sam_read on any other,
+ * give DQ_EINVAL.
+ * Out of scope: interval traversal of SAM (no traversal argument), htsjdk's LENIENT / SILENT
+ * tolerance of malformed lines (the rules hold whatever dq_opts.stringency says), uncompressed
+ * .vcf input, SAM output, sharded and multi-GPU SAM. */
+int dq_sam_open_memory(dq_ctx* ctx, const uint8_t* text, int64_t len);
+int dq_sam_open_path(dq_ctx* ctx, const char* path);
+int dq_sam_run(dq_ctx* ctx, dq_stats* stats); /* records stay in HBM */
+int dq_sam_read(dq_ctx* ctx, int32_t with_raw, dq_batch** out);
+
 /* ---- BGZF compression: the write path -----------------------
  * Replaces htsjdk BlockCompressedOutputStream under HeaderlessBamOutputFormat.BamRecordWriter
  * (D/impl/formats/bam/HeaderlessBamOutputFormat.java:26-50) and BamSink's header file
@@ -418,8 +448,8 @@ void dq_free(void* p);
 
 /* Debug: the device bounds-checked build (`make -C disq_amd/csrc checked` ->
  * libdisq_gpu_checked.so, compiled with -DDQ_CHECKED).  Writes each kernel unit's failed-check
- * count << 32 | largest reported excess << 16 | site bits (K1/K3 kernels, K2 inflate, text,
- * deflate: 4 words) for the current
+ * count << 32 | largest reported excess << 16 | site bits (K1/K3 kernels, K2 inflate, text
+ * with the SAM unit folded in, deflate: 4 words) for the current
  * device and resets them; returns 1 in the checked build, 0 in the product build (words all 0). */
 int dq_checked_report(uint64_t words[4]);
 
