@@ -93,6 +93,12 @@ constexpr int OUTCAP = 65536 + 24;  // + alignment shift (<= 15) + descriptor ov
 #ifndef DQ_RES_QUAD
 #define DQ_RES_QUAD 1
 #endif
+// DQ_RES_SLICE (round 8, the product shape only): 1 = a jump round touches only the 64-byte chunk
+// slices of the wave that still hold a pending byte, under scalar branches on a mask with one
+// bit per slice; 0 = every round of a wave with a pending byte runs its four entries branch-free.
+#ifndef DQ_RES_SLICE
+#define DQ_RES_SLICE 0
+#endif
 constexpr int RES_NXT = DQ_RES_NB * DQ_RES_G * WG;  // resolve batch bytes (NB * G * WG)
 constexpr int NCARRY = (65536 + RES_NXT - 1) / RES_NXT + 1;  // batches of a block (carry slots)
 
@@ -392,6 +398,14 @@ DQ_AI uint32_t zx16(uint16_t v) {
 #else
   return v;
 #endif
+}
+// The same for an entry that was widened where it was read, applied where it is used (the asm
+// waits for the read).
+DQ_AI uint32_t zx32(uint32_t x) {
+#ifndef DQ_NO_ZX16
+  asm("" : "+v"(x));
+#endif
+  return x;
 }
 
 // Second-level / canonical lookup for a root entry that is not a code.  SLOW = false (no E_SLOW
@@ -1697,24 +1711,6 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       }
     }
   };
-  // HYB, after the barrier that follows the first hop: every thread takes the first-hop sources
-  // of its own bytes from nxt (only their owner rewrites them from here on)
-  auto adopt = [&](int32_t b0, int32_t* fr, int32_t* xs, bool& pending) {
-    int32_t qv[NE];
-#pragma unroll
-    for (int e = 0; e < NE; e++) qv[e] = (int32_t)zx16(nxt[(e / G) * CH + G * t + e % G]);
-    pending = false;
-#pragma unroll
-    for (int e = 0; e < NE; e++) {
-      const int32_t x = b0 + (e / G) * CH + G * t + e % G;
-      const int32_t sbk = b0 + (e / G) * CH + ((G * t) & ~511);
-      const int32_t q = qv[e];
-      const bool done = q == x || q < sbk;  // a literal, or a source before the byte's step
-      fr[e] = q;
-      xs[e] = done ? x : q;
-      pending = pending || !done;
-    }
-  };
   // Pointer jumping inside the byte's step: a pending byte reads nxt at its current source and
   // publishes how far it got, so a byte that reads an advanced pointer skips that byte's chain.
   // Every value read is a byte of the same chain, so no barrier orders the rounds and each read
@@ -1751,11 +1747,98 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     }
     pending = any;
   };
+  // HYB (round 8): the rounds on ready LDS offsets.  An entry's state is the byte offset of the
+  // pointer it reads next, relative to its chunk's pointers (ra in [0, 2 * CH): an in-step
+  // source lies in the byte's own chunk, which is its step); a final entry's offset is its own
+  // pointer's, 2 t.  The chunk's offset (e * CH * 2 bytes) is a constant of the entry: the DS
+  // instructions carry it.  With 2 (q - step start) for the pointer q read, "the chain goes on"
+  // is one unsigned compare against ra and the next offset is that value: 4 VALU per entry and
+  // round (7.25 before), 16 VALU per round (29).
+  // `live` is wave-uniform and non-zero while any lane of the wave holds a pending entry; a
+  // wave's entry e is the 64-byte slice of chunk e that its lanes own.  DQ_RES_SLICE = 1 keeps
+  // one bit per slice in it and a round touches only the slices with a pending byte, under
+  // scalar branches (a skipped slice costs no VALU and no DS instruction).  That halves the
+  // entries a round works on and is slower all the same: 2 x 4 branches and their mask
+  // arithmetic per round outweigh 4 VALU per skipped entry on the resolve's critical path
+  // (+0.6 % on the kernel against -3.9 % for the branch-free default, DESIGN.md section 3,
+  // Round 8).
+  constexpr bool SLICE = DQ_RES_SLICE != 0;
+  const uint32_t own2 = 2u * (uint32_t)t;
+  // SLICE: entry e's bit of the live mask (from bit 1: a 0/1 select is compiled as a vector
+  // zero-extend); without SLICE the mask is 0 or LB(0)
+  auto LB = [](int e) { return 2u << e; };
+  auto nxt_at = [&](int e, uint32_t ra) {
+    return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(nxt) + e * (CH * 2) + ra);
+  };
+  // after the barrier that follows the first hop: every thread takes the first-hop sources of
+  // its own bytes from nxt (only their owner rewrites them from here on)
+  auto adopt_live = [&](int32_t b0, int32_t* fr, uint32_t* ra, uint32_t& live) {
+    int32_t qv[NE];
+#pragma unroll
+    for (int e = 0; e < NE; e++) qv[e] = (int32_t)zx16(*nxt_at(e, own2));
+    const uint32_t cb = 2u * (uint32_t)-b0;  // wave-uniform: the batch loop's counter
+    live = 0;
+    uint64_t anym = 0;
+#pragma unroll
+    for (int e = 0; e < NE; e++) {
+      // 2 (q - sbk), sbk = b0 + e * CH the start of the byte's step: past 2^31 for a source
+      // before the step, own2 for a literal (q <= x), so pending is one unsigned compare
+      const uint32_t na = ((uint32_t)qv[e] << 1) + (cb - 2u * e * CH);
+      const bool pend = na < own2;
+      fr[e] = qv[e];
+      ra[e] = pend ? na : own2;
+      if constexpr (SLICE) live |= __ballot(pend) != 0 ? LB(e) : 0u;
+      else anym |= __ballot(pend);
+    }
+    if constexpr (!SLICE) live = anym != 0 ? LB(0) : 0u;
+  };
+  auto jump_round_live = [&](int32_t b0, int32_t* fr, uint32_t* ra, uint32_t& live) {
+    // Two passes, so that the entries' reads are in flight together and waited for once.
+    // A final entry's round is idempotent: it re-reads its own pointer and re-writes the value
+    // nxt[own] holds already, so final lanes take the round branch-free and no lane mask is
+    // kept.  SLICE: an entry whose bit is clear is skipped whole; every lane's entry is final
+    // then, so the skip leaves nxt and the registers as the round would.
+    const uint32_t cb = 2u * (uint32_t)-b0;  // wave-uniform: the batch loop's counter
+#pragma unroll
+    for (int e = 0; e < NE; e++)
+      if (!SLICE || (live & LB(e))) {
+        DQ_CHK(ra[e] < 2u * CH && !(ra[e] & 1u), CHK_K2_NXT);
+        fr[e] = *nxt_at(e, ra[e]);  // (zx16 in the second pass: it would wait for the read here)
+      }
+    uint32_t nl = 0;
+    uint64_t anym = 0;
+#pragma unroll
+    for (int e = 0; e < NE; e++)
+      if (!SLICE || (live & LB(e))) {
+        // the pointer read is the entry's source so far: final when the entry is (a final lane
+        // of a live slice re-read its own pointer, which holds the source it has in fr already),
+        // and replaced by a later round when not
+        const uint32_t q = zx32(fr[e]);
+        fr[e] = (int32_t)q;
+        const uint32_t na = (q << 1) + (cb - 2u * e * CH);  // 2 (q - sbk), one v_lshl_add
+        // the chain runs downwards: q <= p.  It goes on while q lies in the step below p
+        // (na < ra); q == p is a literal and q before the step is final (na wraps past 2^31)
+        const bool pd = ra[e] != own2, lt = na < ra[e];
+        ra[e] = pd && lt ? na : own2;  // (lane masks: a scalar and)
+        if constexpr (SLICE) nl |= (__ballot(pd) & __ballot(lt)) != 0 ? LB(e) : 0u;
+        else anym |= __ballot(pd) & __ballot(lt);
+        *nxt_at(e, own2) = (uint16_t)q;
+      }
+    live = SLICE ? nl : anym != 0 ? LB(0) : 0u;
+  };
   // Software pipeline over batches: while batch k's ordered steps (b) run, batch k+1 takes its
   // first hop (its descriptors are intact until its own steps) and one jump round after each
   // step barrier (nxt holds batch k+1 only: batch k's sources are final in registers by then).
+  // (HYB keeps each batch's pointers as offsets ra* and its pending state as the live mask)
   int32_t frA[NE], xsA[NE];
+  uint32_t raA[NE];
   bool pendA = false;
+  uint32_t liveA = 0;
+  auto left = [&](bool pending, uint32_t live) { return HYB ? live != 0 : pending; };
+  auto round = [&](int32_t b0, int32_t* fr, int32_t* xs, uint32_t* ra, bool& pending, uint32_t& live) {
+    if constexpr (HYB) jump_round_live(b0, fr, ra, live);
+    else jump_round(b0, fr, xs, pending);
+  };
   int32_t cms = -1;     // carry into the current batch
   uint32_t cdesc = 0;
   first_hop(0, cms, cdesc, frA, xsA, pendA);
@@ -1780,17 +1863,22 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     L.u.r.carry_desc[t] = ncdesc;
   }
   __syncthreads();
-  if constexpr (HYB) adopt(0, frA, xsA, pendA);
-  for (int hop = 0; pendA && hop < WG + 2; hop++) jump_round(0, frA, xsA, pendA);
-  for (int32_t bs = 0; bs < rsize; bs += BATCH) {
+  if constexpr (HYB) adopt_live(0, frA, raA, liveA);
+  for (int hop = 0; left(pendA, liveA) && hop < WG + 2; hop++) round(0, frA, xsA, raA, pendA, liveA);
+  // (HYB: the loop's bound as a scalar, so that the batch start and the live mask set under
+  // `more` are wave-uniform for the compiler)
+  const int32_t rsize_u = HYB ? __builtin_amdgcn_readfirstlane(rsize) : rsize;
+  for (int32_t bs = 0; bs < rsize_u; bs += BATCH) {
     const uint64_t tb0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     const int32_t nbs = bs + BATCH;
-    const bool more = nbs < rsize;
+    const bool more = nbs < rsize_u;
     __syncthreads();  // every wave's jumps of batch k are done: nxt is free for batch k+1
     const int32_t ncms = more ? L.u.r.carry_ms[bs / BATCH] : -1;
     const uint32_t ncdesc = more ? L.u.r.carry_desc[bs / BATCH] : 0u;
     int32_t frB[NE], xsB[NE];
+    uint32_t raB[NE];
     bool pendB = false;
+    uint32_t liveB = 0;
     if (more) first_hop(nbs, ncms, ncdesc, frB, xsB, pendB);
     const uint64_t tb1 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     // (b) batch k's 512-byte steps in order: one LDS read + write per copied byte, one barrier.
@@ -1810,8 +1898,8 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
             v[i] = O[INR ? frA[k * G + i] : min(frA[k * G + i], 65535)];
           }
         if constexpr (HYB)  // the first barrier after the next batch's first hop has passed
-          if (k == 1 && more) adopt(nbs, frB, xsB, pendB);
-        if ((k > 0 || j > 0) && pendB) jump_round(nbs, frB, xsB, pendB);
+          if (k == 1 && more) adopt_live(nbs, frB, raB, liveB);
+        if ((k > 0 || j > 0) && left(pendB, liveB)) round(nbs, frB, xsB, raB, pendB, liveB);
         if constexpr (QUAD && INR) {
           // the group's four bytes in one to three stores by the image's alignment (uniform): a
           // byte at or past rsize is its own source, so it rewrites its own value like a literal
@@ -1842,7 +1930,7 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
         __syncthreads();
       }
     }
-    if (pendB) jump_round(nbs, frB, xsB, pendB);
+    if (left(pendB, liveB)) round(nbs, frB, xsB, raB, pendB, liveB);
     const uint64_t tb2 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     // (c) store the 16-byte U lines this batch completed
     const int32_t c1 = min(rsize, nbs);
@@ -1857,7 +1945,7 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       lines_done = lines_to;
     }
     const uint64_t tb3 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
-    for (int hop = 0; pendB && hop < WG + 2; hop++) jump_round(nbs, frB, xsB, pendB);
+    for (int hop = 0; left(pendB, liveB) && hop < WG + 2; hop++) round(nbs, frB, xsB, raB, pendB, liveB);
 #pragma unroll
     for (int e = 0; e < NE; e++) frA[e] = frB[e];
     cms = ncms;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B of compile-time kernel variants: each argument names a prebuilt library under
 # disq_amd/_build/ (e.g. libdisq_gpu.so libdisq_gpu_b.so); plain + phase timing for each, twice,
-# interleaved (REPS=n for n alternations).  usage: tools/gpu_variant_ab.sh TAG LIB...
+# interleaved (REPS=n for n alternations, SAMPLES=n for n samples per process: tools/inflate_timing.py).
+# usage: tools/gpu_variant_ab.sh TAG LIB...
 set -eo pipefail
 tag=$1; shift
 out=gpurun_out/$tag

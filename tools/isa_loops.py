@@ -10,9 +10,13 @@ and the common-path (non-SLOW) instantiation are listed.
 
 --resolve: the resolve's batch loop (the depth-1 loop with the match-start search, v_ffbh, and the
 step barriers) split by basic block into the next batch's first hop (up to the first step's byte
-reads), the jump rounds (blocks that read a next pointer per entry: the scheduler may merge a
-step's byte read or store into them), the U store and the rest of the ordered steps.  Counts are
-per thread and batch; the rare modulo path (v_rcp_f32) is listed apart.
+reads), the hand-over (four next-pointer reads and no pointer store: the group pointers' adoption),
+the jump rounds (blocks that read a next pointer per entry: the scheduler may merge a step's byte
+read or store into them), the U store and the rest of the ordered steps.  Counts are per thread
+and batch; the rare modulo path (v_rcp_f32) is listed apart.  With -DDQ_RES_SLICE=1 a round is
+split up under scalar branches on its live mask: a read block per entry (one ds_read_u16), an
+update block per entry (one ds_write_b16) and the blocks of the mask tests between them, which
+are all that a round executes when no entry is live; the tool reports the VALU of each kind.
 """
 import os
 import re
@@ -47,7 +51,7 @@ def loops(lines):
             continue
         name = m.group(1)
         last = None
-        for j in range(i + 1, min(len(lines), i + 900)):
+        for j in range(i + 1, min(len(lines), i + 3000)):
             if re.search(r"s_(cbranch_\w+|branch)\s+" + re.escape(name) + r"$", lines[j].strip()):
                 last = j
         if last is None:
@@ -92,6 +96,7 @@ def resolve(ker):
                 break
     cnt = lambda b, op: sum(x.startswith(op) for x in b)  # noqa: E731
     state, tot, rounds = "first hop", {}, []
+    split = {"read": [], "update": [], "test": []}
     print(f"resolve batch loop {best[0]}: {len(best[1])} instructions")
     for name, b in blocks:
         if not b:
@@ -101,22 +106,39 @@ def resolve(ker):
         kind = state
         if cnt(b, "v_rcp_f32"):
             kind = "modulo path"
+        elif state == "steps" and cnt(b, "ds_read_u16") >= 4 and not cnt(b, "ds_write_b16"):
+            kind = "hand-over"
         elif state == "steps" and cnt(b, "ds_read_u16") >= 4:
             kind = "jump round"
             rounds.append(cnt(b, "v_"))
+        elif state == "steps" and cnt(b, "ds_read_u16") == 1 and cnt(b, "ds_") == 1:
+            kind = "round read"
+            split["read"].append(cnt(b, "v_"))
+        elif state == "steps" and cnt(b, "ds_write_b16") == 1 and not cnt(b, "ds_read"):
+            kind = "round update"
+            split["update"].append(cnt(b, "v_"))
+        elif state == "steps" and cnt(b, "s_bitcmp1_b32") and not cnt(b, "ds_") and not cnt(b, "s_barrier"):
+            kind = "round test"
+            split["test"].append(cnt(b, "v_"))
         elif state == "steps" and cnt(b, "global_store"):
             kind = "U store"
         v, sa, d = cnt(b, "v_"), cnt(b, "s_"), cnt(b, "ds_")
         t = tot.setdefault(kind, [0, 0, 0, 0])
         for i, q in enumerate((v, sa, d, cnt(b, "v_ffbh"))):
             t[i] += q
-        if v + d > 3:
+        if v + d > 3 or kind.startswith("round "):
             print(f"  {name:12s} {kind:12s} VALU {v:4d}  SALU {sa:4d}  DS {d:3d}  ffbh {cnt(b, 'v_ffbh')}"
                   f"  ds_write_b64 {cnt(b, 'ds_write_b64')}  barriers {cnt(b, 's_barrier')}")
     for k, t in tot.items():
         print(f"{k:12s} VALU {t[0]:4d}  SALU {t[1]:4d}  DS {t[2]:3d}  ffbh {t[3]}")
     if rounds:
         print("jump rounds:", " ".join(map(str, rounds)), "VALU each")
+    if split["read"] or split["update"]:
+        r, u = max(split["read"] or [0]), max(split["update"] or [0])
+        print(f"split rounds: {len(split['read'])} read blocks of at most {r} VALU (a read block holds the next "
+              f"entry's mask test too), {len(split['update'])} update blocks of at most {u} VALU:")
+        print(f"  a live entry costs at most {r + u} VALU; a round with no live entry runs the mask tests alone: "
+              f"{max(split['read'] + split['test'] + [0])} VALU in any block of them")
 
 
 def main():

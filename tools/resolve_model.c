@@ -16,14 +16,24 @@
 //   - --pending: bytes still pending after the first hop (a copy whose source lies in the byte's
 //     own 512-byte step), per wave of 64 lanes holding one byte (64 bytes) or four contiguous
 //     bytes (256 bytes: the first and second half of a step) per lane.
+//   - --rounds: the jump rounds of the product shape, simulated synchronously (every read of a
+//     round sees the pointers as the round before left them).  A batch is 2048 bytes, four chunks
+//     of 512 (each one step); wave w of eight owns bytes 64 w .. 64 w + 63 of each chunk, its four
+//     slices, one byte of each per lane (a lane's four entries).  A wave runs a round while any
+//     of its bytes is pending.  Reported: rounds per wave and batch, and the entry operations per
+//     thread and batch when a running wave works on all four entries (whole-wave skip), only on
+//     its slices with a pending byte (slice skip), or on its pending bytes compacted onto its
+//     lanes (one entry per 64 pending bytes); per round, the running waves per batch, the pending
+//     bytes and the slices with a pending byte per running wave.
 // Development tool (not built by the product, not a test): cc -O2 -o /tmp/rm tools/resolve_model.c
-//   /tmp/rm file.bam [maxblocks] [--nibbles] [--pending]
+//   /tmp/rm file.bam [maxblocks] [--nibbles] [--pending] [--rounds]
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 typedef struct { int32_t pos, len, dist; } Tok;  // len 0: literal
+#define RMAX 16
 static int32_t src1[70000], nx[70000], hop[70000];  // per byte: first-hop source, jump scratch
 
 static const uint8_t *g_in;
@@ -153,11 +163,14 @@ typedef struct {
   long nib[16], groups;
   // [0] one byte per lane, [1] four per lane first half of a step, [2] second half
   long pw_waves[3], pw_bytes[3], pw_lanes[3], pw_empty[3], pend_bytes;
+  // --rounds: per round (the last row collects the rounds past it) running waves, their pending
+  // bytes and live slices, the compacted entries; batches
+  long jr_waves[RMAX], jr_pend[RMAX], jr_slices[RMAX], jr_compact[RMAX], jr_batches, jr_maxround;
 } Stats;
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s file.bam [maxblocks] [--nibbles] [--pending]\n", argv[0]);
+    fprintf(stderr, "usage: %s file.bam [maxblocks] [--nibbles] [--pending] [--rounds]\n", argv[0]);
     return 2;
   }
   FILE *f = fopen(argv[1], "rb");
@@ -169,10 +182,11 @@ int main(int argc, char **argv) {
   if (fread(buf, 1, (size_t)fl, f) != (size_t)fl) return 2;
   fclose(f);
   long maxb = 1L << 40;
-  int opt_nib = 0, opt_pend = 0;
+  int opt_nib = 0, opt_pend = 0, opt_rounds = 0;
   for (int i = 2; i < argc; i++) {
     if (!strcmp(argv[i], "--nibbles")) opt_nib = 1;
     else if (!strcmp(argv[i], "--pending")) opt_pend = 1;
+    else if (!strcmp(argv[i], "--rounds")) opt_rounds = 1;
     else maxb = atol(argv[i]);
   }
   Stats S;
@@ -350,6 +364,49 @@ int main(int argc, char **argv) {
         S.pw_empty[k] += n == 0;
       }
     }
+    if (opt_rounds) {  // the jump rounds of every batch of 2048 bytes, synchronously
+      static int32_t pt[2048], nn[2048];  // per byte of the batch: where it reads next (own: final)
+      for (int b0 = 0; b0 < ol; b0 += 2048) {
+        int n = ol - b0 < 2048 ? ol - b0 : 2048;
+        for (int i = 0; i < n; i++) {
+          int x = b0 + i;
+          nx[x] = src1[x];  // the first hop's pointer (a literal points at itself)
+          pt[i] = src1[x] != x && src1[x] >= (x & ~511) ? src1[x] : x;
+        }
+        S.jr_batches++;
+        for (int r = 0;; r++) {
+          int rr = r < RMAX ? r : RMAX - 1, any = 0;
+          for (int w = 0; w < 8; w++) {
+            int pend = 0, slices = 0;
+            for (int k = 0; k < 4; k++) {
+              int c = 0;
+              for (int l = 0; l < 64; l++) {
+                int i = 512 * k + 64 * w + l;
+                c += i < n && pt[i] != b0 + i;
+              }
+              pend += c;
+              slices += c != 0;
+            }
+            if (!pend) continue;
+            any = 1;
+            S.jr_waves[rr]++;
+            S.jr_pend[rr] += pend;
+            S.jr_slices[rr] += slices;
+            S.jr_compact[rr] += (pend + 63) / 64;
+          }
+          if (!any) break;
+          if (r + 1 > S.jr_maxround) S.jr_maxround = r + 1;
+          for (int i = 0; i < n; i++) {  // every pending byte reads the pointer at its source
+            int x = b0 + i, q = nx[pt[i]];
+            nn[i] = nx[x];
+            if (pt[i] == x) continue;
+            nn[i] = q;
+            pt[i] = q == pt[i] || q < (x & ~511) ? x : q;  // a literal or before the step: final
+          }
+          for (int i = 0; i < n; i++) nx[b0 + i] = nn[i];
+        }
+      }
+    }
     {  // step DAG (512-byte steps): final source of each byte after in-step resolution
       static int32_t fin[70000], sd[200];
       int ns = (ol + 511) / 512;
@@ -443,7 +500,27 @@ int main(int argc, char **argv) {
     printf("  4 bytes per lane, all waves: lanes with a pending byte %.1f %%\n",
            100.0 * (S.pw_lanes[1] + S.pw_lanes[2]) / (64.0 * (S.pw_waves[1] + S.pw_waves[2])));
   }
-  if (opt_nib || opt_pend) return 0;
+  if (opt_rounds) {
+    double nb = (double)S.jr_batches;
+    long wr = 0, sl = 0, cp = 0;
+    for (int r = 0; r < RMAX; r++) {
+      wr += S.jr_waves[r];
+      sl += S.jr_slices[r];
+      cp += S.jr_compact[r];
+    }
+    printf("jump rounds, synchronous, %ld blocks, %ld batches of 2048 bytes (8 waves, 4 entries per thread):\n",
+           S.blocks, S.jr_batches);
+    printf("  wave-rounds that run per batch                      %6.2f  (%.2f rounds per wave; most rounds in a batch %ld)\n",
+           wr / nb, wr / nb / 8, S.jr_maxround);
+    printf("  entry operations per thread and batch, whole-wave skip (4 per running round)  %5.2f\n", 4 * wr / nb / 8);
+    printf("  the same, an entry only when its 64-byte slice holds a pending byte           %5.2f\n", sl / nb / 8);
+    printf("  the same, pending bytes compacted inside the wave (one entry per 64 pending)  %5.2f\n", cp / nb / 8);
+    for (int r = 0; r < RMAX && S.jr_waves[r]; r++)
+      printf("  round %2d%s running waves per batch %5.2f  pending bytes per running wave %5.1f  slices with a pending byte %4.2f of 4\n",
+             r, r == RMAX - 1 ? "+:" : ": ", S.jr_waves[r] / nb, (double)S.jr_pend[r] / S.jr_waves[r],
+             (double)S.jr_slices[r] / S.jr_waves[r]);
+  }
+  if (opt_nib || opt_pend || opt_rounds) return 0;
   printf("blocks %ld  bytes/block %.0f  tokens/block %.0f  literals/block %.0f  matches/block %.0f\n",
          S.blocks, S.bytes / B, S.toks / B, S.lits / B, S.matches / B);
   printf("bytes in matches %.1f %%  mean match length %.2f  overlapping (dist < len) %.2f %%  dist < 16 %.2f %%\n",
