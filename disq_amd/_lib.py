@@ -115,7 +115,7 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_text_set_index", "dq_text_set_intervals", "dq_decode_file_multi",
            "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai",
            "dq_text_write_tbi", "dq_sam_open_memory", "dq_sam_open_path", "dq_sam_run",
-           "dq_sam_read")
+           "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch")
 
 _lib = None
 _lock = threading.Lock()
@@ -190,6 +190,10 @@ def lib():
         L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
         L.dq_sam_run.argtypes = [vp, P(DqStats)]
         L.dq_sam_read.argtypes = [vp, C.c_int32, P(P(DqBatch))]
+        L.dq_sam_write.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, P(C.c_void_p),
+                                   P(C.c_int64)]
+        L.dq_sam_write_resident.argtypes = [vp, P(C.c_int64), P(C.c_double)]
+        L.dq_sam_write_fetch.argtypes = [vp, vp, C.c_int64]
         L.dq_bgzf_compress.argtypes = [vp, vp, C.c_int64, P(C.c_void_p), P(C.c_int64)]
         L.dq_bgzf_compress_resident.argtypes = [vp, P(C.c_int64), P(C.c_double)]
         L.dq_bgzf_fetch.argtypes = [vp, vp, C.c_int64]
@@ -552,6 +556,48 @@ class Context:
         bp = C.POINTER(DqBatch)()
         check(self._h, lib().dq_sam_read(self._h, export_mode(with_raw), C.byref(bp)))
         return batch_to_numpy(bp, self)
+
+    # ---- SAM output
+    def sam_write(self, header_raw, raw, raw_offset=None) -> bytes:
+        """SamSink's part file (dq_sam_write): the records `raw` (back to back; raw_offset = their
+        offsets as read(with_raw=True) gives them, or None for the block_size chain) as SAM lines,
+        each followed by LF.  header_raw = the BAM header, whose references name RNAME / RNEXT."""
+        hdr = np.frombuffer(header_raw, np.uint8)
+        buf = np.ascontiguousarray(np.frombuffer(raw, np.uint8) if not isinstance(raw, np.ndarray) else raw)
+        if raw_offset is None:
+            off, n = None, None
+        else:
+            off = np.ascontiguousarray(raw_offset, np.int64)
+            n = len(off)
+        if n is None:  # the records the chain holds (a plain loop: pass raw_offset for large inputs)
+            n, p = 0, 0
+            while p < len(buf):
+                n += 1
+                bs = int.from_bytes(bytes(buf[p:p + 4]), "little", signed=True) if p + 4 <= len(buf) else -1
+                if bs < 0:
+                    break
+                p += 4 + bs
+        out, m = C.c_void_p(), C.c_int64()
+        check(self._h, lib().dq_sam_write(self._h, hdr.ctypes.data, len(hdr),
+                                          buf.ctypes.data if len(buf) else None, len(buf),
+                                          off.ctypes.data if off is not None and len(off) else None, n,
+                                          C.byref(out), C.byref(m)))
+        try:
+            return _copy_out(out.value, m.value)
+        finally:
+            lib().dq_free(out)
+
+    def sam_write_resident(self):
+        """Every record of the open whole file as SAM text, left in HBM (dq_sam_write_resident):
+        (text length, device ms)."""
+        n, ms = C.c_int64(), C.c_double()
+        check(self._h, lib().dq_sam_write_resident(self._h, C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+    def sam_write_fetch(self, n) -> np.ndarray:
+        out = np.zeros(max(1, n), np.uint8)
+        check(self._h, lib().dq_sam_write_fetch(self._h, out.ctypes.data, n))
+        return out[:n]
 
     def set_index(self, bai_bytes):
         if bai_bytes is None:

@@ -160,6 +160,10 @@ struct dq_ctx {
   unsigned long long sam_init[4] = {~0ull, 0, 0, 0};  // first failing line | undecided | fix-ups
   DevBuf s_ls, s_vs, s_vl, s_splits, s_status, s_size, s_fix, s_refs, sam_rec;
   dq::SamRefs sam_refs{};
+  // SAM writer (dq_sam_write*): the uploaded records and offsets, per record status / line size /
+  // line offset, the reference names, the text (w_len bytes)
+  DevBuf w_in, w_off, w_status, w_size, w_loff, w_refs, w_scal, w_out;
+  int64_t w_len = 0;
   // BGZF deflate (write path)
   DevBuf z_in, z_stage, z_link, z_slots, z_size, z_off, z_out;
   int64_t z_len = 0;
@@ -3664,6 +3668,178 @@ int dq_sam_read(dq_ctx* ctx, int32_t with_raw, dq_batch** out) {
   return make_batch(ctx, ranges, nullptr, with_raw, bounds, out);
 }
 
+// ---- SAM writer (row f8): SamSink.save's part file.  Size pass, the first failing record, scan of
+// the sizes, format pass (dq_samw.hip); the text stays in ctx->w_out.
+static int samw_run(dq_ctx* ctx, const std::vector<std::string>& names, const uint8_t* d_raw,
+                    int64_t raw_len, const int64_t* d_off, int64_t n, double* ms) {
+  hipStream_t s = ctx->s;
+  ctx->w_len = 0;
+  if (ms) *ms = 0;
+  int rc;
+  {  // the reference names: n + 1 offsets | name bytes
+    const size_t nr = names.size();
+    std::vector<int32_t> off(nr + 1, 0);
+    std::string bytes;
+    for (size_t r = 0; r < nr; r++) {
+      bytes += names[r];
+      off[r + 1] = (int32_t)bytes.size();
+    }
+    if (bytes.size() > (size_t)INT32_MAX) RET(DQ_EINVAL, "reference names longer than 2^31-1 bytes");
+    std::vector<uint8_t> buf(4 * (nr + 1) + bytes.size() + 8);
+    memcpy(buf.data(), off.data(), 4 * (nr + 1));
+    memcpy(buf.data() + 4 * (nr + 1), bytes.data(), bytes.size());
+    if ((rc = ensure_all(ctx, ctx->w_refs, buf.size()))) return rc;
+    HIPCHK(hipMemcpy(ctx->w_refs.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  }
+  const SamwRefs refs{ctx->w_refs.as<int32_t>(), ctx->w_refs.as<uint8_t>() + 4 * (names.size() + 1),
+                      (int32_t)names.size()};
+  const size_t n1 = (size_t)std::max<int64_t>(1, n);
+  if ((rc = ensure_all(ctx, ctx->w_status, 4 * n1)) || (rc = ensure_all(ctx, ctx->w_size, 8 * n1)) ||
+      (rc = ensure_all(ctx, ctx->w_loff, 8 * (n1 + 1))) || (rc = ensure_scan(ctx, n)) ||
+      (rc = ensure_all(ctx, ctx->w_scal, 64)))
+    return rc;
+  if (n == 0) return ensure_all(ctx, ctx->w_out, 64);
+  unsigned long long* d_scal = ctx->w_scal.as<unsigned long long>();
+  unsigned long long sc[2] = {~0ull, ~0ull};
+  HIPCHK(hipEventRecord(ctx->ev[0], s));
+  HIPCHK(hipMemcpyAsync(d_scal, sc, sizeof sc, hipMemcpyHostToDevice, s));
+  launch_samw_sizes(d_raw, raw_len, d_off, n, refs, ctx->w_status.as<int32_t>(), ctx->w_size.as<int64_t>(),
+                    d_scal, s);
+  launch_exclusive_scan_i64(ctx->w_size.as<int64_t>(), ctx->w_loff.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
+  int64_t total = 0;
+  HIPCHK(hipMemcpyAsync(sc, d_scal, sizeof sc, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, ctx->w_loff.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (sc[0] != ~0ull) {
+    const int64_t j = (int64_t)sc[0];
+    if (j < 0 || j >= n) RET(DQ_EDEVICE, "SAM writer size pass: bad failing-record index");
+    int32_t st = 0;
+    HIPCHK(hipMemcpy(&st, ctx->w_status.as<int32_t>() + j, 4, hipMemcpyDeviceToHost));
+    char nb[8];
+    RET(DQ_EFORMAT, "record " + std::to_string(j) + ": " + dqs::sam_status_name(st, nb));
+  }
+  if (sc[1] != ~0ull)
+    RET(DQ_EINVAL, "record " + std::to_string((long long)sc[1]) + ": a line longer than 2147483647 bytes");
+  if (total < n) RET(DQ_EDEVICE, "SAM writer size pass: bad text bytes total");
+  if ((rc = ensure_all(ctx, ctx->w_out, (size_t)total + 64))) return rc;
+  const bool direct = getenv("DQ_SAMW_DIRECT") != nullptr;  // A/B (tools/sam_write_bench.py): no LDS tile
+  launch_samw_format(d_raw, raw_len, d_off, n, refs, ctx->w_loff.as<int64_t>(), ctx->w_out.as<uint8_t>(),
+                     direct ? 0 : 1, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ev[1], s));
+  HIPCHK(hipStreamSynchronize(s));
+  ctx->w_len = total;
+  if (ms) *ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+  return 0;
+}
+
+// The reference names of a BAM header's bytes (magic, l_text, text, n_ref, references).
+static int samw_header_names(dq_ctx* ctx, const uint8_t* h, int64_t n, std::vector<std::string>& names) {
+  if (!h || n < 12 || memcmp(h, "BAM\1", 4) != 0) RET(DQ_EFORMAT, "Invalid BAM file header");
+  const int32_t l_text = rd32(h + 4);
+  if (l_text < 0 || 8 + (int64_t)l_text + 4 > n) RET(DQ_EFORMAT, "Invalid BAM header text length");
+  int64_t p = 8 + (int64_t)l_text;
+  const int32_t nr = rd32(h + p);
+  p += 4;
+  if (nr < 0) RET(DQ_EFORMAT, "Invalid reference count");
+  for (int32_t i = 0; i < nr; i++) {
+    if (p + 4 > n) RET(DQ_EFORMAT, "truncated BAM header");
+    const int32_t ln = rd32(h + p);
+    if (ln <= 1 || p + 8 + (int64_t)ln > n) RET(DQ_EFORMAT, "Invalid BAM file header: missing sequence name");
+    names.emplace_back((const char*)h + p + 4, (size_t)ln - 1);
+    p += 8 + (int64_t)ln;
+  }
+  return 0;
+}
+
+int dq_sam_write(dq_ctx* ctx, const uint8_t* header, int64_t header_len, const uint8_t* raw,
+                 int64_t raw_len, const int64_t* raw_offset, int64_t n_records, uint8_t** out,
+                 int64_t* out_len) {
+  if (!ctx || !out || !out_len || raw_len < 0 || n_records < 0 || (!raw && raw_len > 0)) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  *out_len = 0;
+  std::vector<std::string> names;
+  int rc = samw_header_names(ctx, header, header_len, names);
+  if (rc) return rc;
+  // the records' offsets: the caller's, or the block_size chain; a chain that breaks at record k
+  // (or does not end at raw_len) is that record's "fields", after the records before it
+  std::vector<int64_t> off((size_t)n_records);
+  int64_t n = n_records, broken = -1;
+  if (raw_offset) {
+    for (int64_t k = 0; k < n_records; k++) {
+      if (raw_offset[k] < 0 || raw_offset[k] > raw_len - 4) RET(DQ_EINVAL, "raw_offset outside the records' bytes");
+      off[(size_t)k] = raw_offset[k];
+    }
+  } else {
+    int64_t p = 0;
+    for (int64_t k = 0; k < n_records; k++) {
+      int32_t bs = -1;
+      if (p + 4 <= raw_len) bs = rd32(raw + p);
+      if (bs < 0 || p + 4 + (int64_t)bs > raw_len) {
+        broken = n = k;
+        break;
+      }
+      off[(size_t)k] = p;
+      p += 4 + (int64_t)bs;
+    }
+    if (broken < 0 && p != raw_len) broken = n_records;
+  }
+  if ((rc = ensure_all(ctx, ctx->w_in, (size_t)raw_len + 64)) ||
+      (rc = ensure_all(ctx, ctx->w_off, 8 * (size_t)std::max<int64_t>(1, n))))
+    return rc;
+  if (raw_len) HIPCHK(hipMemcpy(ctx->w_in.p, raw, (size_t)raw_len, hipMemcpyHostToDevice));
+  if (n) HIPCHK(hipMemcpy(ctx->w_off.p, off.data(), 8 * (size_t)n, hipMemcpyHostToDevice));
+  if ((rc = samw_run(ctx, names, ctx->w_in.as<uint8_t>(), raw_len, ctx->w_off.as<int64_t>(), n, nullptr)))
+    return rc;
+  if (broken >= 0) RET(DQ_EFORMAT, "record " + std::to_string(broken) + ": fields");
+  uint8_t* b = (uint8_t*)malloc((size_t)std::max<int64_t>(1, ctx->w_len));
+  if (!b) return DQ_ENOMEM;
+  if (ctx->w_len && (rc = d2h_large(ctx, b, ctx->w_out.p, (size_t)ctx->w_len))) {
+    free(b);
+    return rc;
+  }
+  *out = b;
+  *out_len = ctx->w_len;
+  return 0;
+}
+
+int dq_sam_write_resident(dq_ctx* ctx, int64_t* out_len, double* ms) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  ctx->w_len = 0;
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  if (ctx->shard) RET(DQ_EINVAL, "dq_sam_write_resident writes a whole file, not a shard");
+  if (ctx->text_mode) RET(DQ_EINVAL, "a text (VCF) context holds no records");
+  int rc;
+  int64_t raw_len = 0;
+  if (ctx->sam_mode) {
+    if ((rc = sam_run(ctx))) return rc;
+    if ((rc = get_i64(ctx, ctx->rec_lin.as<int64_t>() + ctx->nrec, &raw_len))) return rc;
+    if (ctx->nrec == 0) raw_len = 0;
+  } else {  // every record once, in file order: the index-only run dq_write_bai makes
+    ctx->have_pipeline = false;
+    ctx->index_only = true;
+    rc = run_pipeline(ctx);
+    ctx->index_only = false;
+    ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
+    if (rc) return rc;
+    raw_len = ctx->ulen;
+  }
+  if ((rc = samw_run(ctx, ctx->ref_name, ctx->rec_src(), raw_len, ctx->rec_lin.as<int64_t>(), ctx->nrec, ms)))
+    return rc;
+  if (out_len) *out_len = ctx->w_len;
+  return 0;
+}
+
+int dq_sam_write_fetch(dq_ctx* ctx, uint8_t* host_out, int64_t cap) {
+  if (!ctx || (!host_out && cap > 0)) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  if (cap < ctx->w_len) RET(DQ_EINVAL, "buffer smaller than the SAM text");
+  if (ctx->w_len) return d2h_large(ctx, host_out, ctx->w_out.p, (size_t)ctx->w_len);
+  return 0;
+}
+
 int dq_text_run(dq_ctx* ctx, int32_t drop_header_lines, dq_stats* stats) {
   if (!ctx) return DQ_EINVAL;
   ON_DEVICE(ctx);
@@ -4090,6 +4266,16 @@ int dq_checked_report(uint64_t words[4]) {
   words[2] = dq::dq_chk_take_text();
   {  // the SAM unit shares the text word: counts added, excess by maximum, site bits OR-ed
     const uint64_t a = words[2], b = dq::dq_chk_take_sam();
+    if (a == ~0ull || b == ~0ull) {
+      words[2] = ~0ull;
+    } else {
+      const uint64_t cnt = std::min<uint64_t>(0xffffffffull, (a >> 32) + (b >> 32));
+      const uint64_t ex = std::max((a >> 16) & 0xffff, (b >> 16) & 0xffff);
+      words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
+    }
+  }
+  {  // and so does the SAM writer's unit
+    const uint64_t a = words[2], b = dq::dq_chk_take_samw();
     if (a == ~0ull || b == ~0ull) {
       words[2] = ~0ull;
     } else {

@@ -45,7 +45,8 @@ enum : int {
   CHK_K3_SPEC = 13,  // K3: the LDS-filtered segment speculation differs from seg_spec_kernel<64>
   CHK_BAI = 14,      // .bai build: a linear window, perm slot, chunk or bin outside its table
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
-  CHK_SAM = 15,      // SAM read (dq_sam.hip shares the bit): a line, size, record-byte or fix-up slot
+  CHK_SAM = 15,      // SAM read and write (dq_sam.hip, dq_samw.hip share the bit): a line, size,
+                     //     record-byte, line-byte or fix-up slot
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -422,8 +423,28 @@ void launch_sam_encode(const uint8_t* T, const int64_t* lstart, const int64_t* v
                        const int64_t* roff, const int32_t* size, uint8_t* rec, RecSoA soa,
                        int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt, hipStream_t s);
 
+// ------------------------------------------------------------------ SAM writer (dq_samw.hip)
+struct SamwRefs {           // the header's reference names by index, see dq_samw_core.h
+  const int32_t* name_off;  // n + 1 offsets into names
+  const uint8_t* names;
+  int32_t n;
+};
+int32_t samw_tile_bytes();  // line bytes one workgroup's LDS tile takes
+// Size pass over the n records at raw[off[j]] (raw_len readable bytes): status[j], size[j] = the
+// line's bytes with its LF; scal[0] (all ones) takes the smallest failing j, scal[1] (all ones) the
+// smallest j whose line is longer than 2^31-1 bytes.
+void launch_samw_sizes(const uint8_t* raw, int64_t raw_len, const int64_t* off, int64_t n,
+                       SamwRefs refs, int32_t* status, int64_t* size, unsigned long long* scal,
+                       hipStream_t s);
+// Format pass: line j at text[loff[j]], loff[n] = total bytes (text: 16-byte aligned for the tile
+// path; use_tile 0: every line straight to memory).
+void launch_samw_format(const uint8_t* raw, int64_t raw_len, const int64_t* off, int64_t n,
+                        SamwRefs refs, const int64_t* loff, uint8_t* text, int32_t use_tile,
+                        hipStream_t s);
+
 // DQ_CHECKED: each kernel unit's check words (count << 32 | site bits), read and reset
 uint64_t dq_chk_take_sam();
+uint64_t dq_chk_take_samw();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

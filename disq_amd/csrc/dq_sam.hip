@@ -14,8 +14,8 @@
 //   encode     the records back to back in line order at the scanned offsets, the SoA rows from
 //              the parsed fields, undecided floats listed for the host.
 // voffset is the offset of the line's first byte in the file: SAM text has no virtual offsets.
-// Out of scope: interval traversal, LENIENT / SILENT tolerance of malformed lines, SAM output,
-// sharded and multi-GPU SAM.
+// Out of scope: interval traversal, LENIENT / SILENT tolerance of malformed lines, sharded and
+// multi-GPU SAM.  (SAM output is dq_samw.hip.)
 #include "dq_internal.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)

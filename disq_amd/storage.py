@@ -277,6 +277,10 @@ class HtsjdkReadsRddStorage:
         header = rdd.getHeader()
         if not header.raw:
             raise ValueError("header has no BAM encoding")
+        if path.endswith(".sam"):  # SamFormat.formatWriteOptionFromPath
+            if bai or sbi:
+                raise ValueError(f"{path}: a .bai / .sbi index needs a BAM path, not SAM text")
+            return self._write_sam(rdd, path, tempPartsDirectory)
         eof = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
         with _lib.Context(device=self._device) as ctx:
             pieces = [ctx.bgzf_compress(header.raw)]
@@ -305,6 +309,40 @@ class HtsjdkReadsRddStorage:
                 if sbi:
                     with open(path + ".sbi", "wb") as fh:
                         fh.write(ctx.write_sbi(sbiGranularity))
+        return path
+
+    def _write_sam(self, rdd: HtsjdkReadsRdd, path: str, tempPartsDirectory: Optional[str]):
+        """SamSink.save (D/impl/formats/sam/SamSink.java:31-49): every read as
+        SAMRecord.getSAMString, trimmed, one per line (dq_sam_write formats each partition on the
+        GPU; an empty partition gives an empty part), the header as its own file, then the parts
+        merged in partition order (Merger.mergeParts) into `path`; the temporary parts directory
+        is deleted after the merge.  The header file is the text inside header.raw, ending in one
+        newline, not re-encoded from a SAMFileHeader (the caveat of the BAM writer above)."""
+        import struct
+        header = rdd.getHeader()
+        l_text = struct.unpack_from("<i", header.raw, 4)[0]
+        text = bytes(header.raw[8:8 + l_text]).rstrip(b"\0")
+        if text and not text.endswith(b"\n"):
+            text += b"\n"
+        pieces = [text]
+        with _lib.Context(device=self._device) as ctx:
+            for p in rdd.getReads().partitions:
+                if p.raw is None or len(p) == 0:
+                    pieces.append(b"")
+                else:
+                    pieces.append(ctx.sam_write(header.raw, p.raw, p.fields["raw_offset"]))
+        if tempPartsDirectory:
+            os.makedirs(tempPartsDirectory, exist_ok=True)
+            names = ["header"] + [f"part-r-{i:05d}" for i in range(len(pieces) - 1)]
+            for n, d in zip(names, pieces):
+                with open(os.path.join(tempPartsDirectory, n), "wb") as fh:
+                    fh.write(d)
+        with open(path, "wb") as fh:
+            for d in pieces:
+                fh.write(d)
+        if tempPartsDirectory:  # fileSystemWrapper.delete(tempPartsDirectory)
+            import shutil
+            shutil.rmtree(tempPartsDirectory, ignore_errors=True)
         return path
 
     @staticmethod

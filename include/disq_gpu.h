@@ -26,6 +26,8 @@
  *     AbstractBinarySamSource.java:87-91 requires for an interval traversal)    dq_write_bai
  *   SamSource.getReads, whole RDD of a SAM text file
  *     (D/impl/formats/sam/SamSource.java:36-77)                             dq_sam_read
+ *   SamSink.save's part file: SAMRecord.getSAMString, String.trim, a LF per read
+ *     (D/impl/formats/sam/SamSink.java:37)                                  dq_sam_write
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -412,11 +414,38 @@ int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms);
  * give DQ_EINVAL.
  * Out of scope: interval traversal of SAM (no traversal argument), htsjdk's LENIENT / SILENT
  * tolerance of malformed lines (the rules hold whatever dq_opts.stringency says), uncompressed
- * .vcf input, SAM output, sharded and multi-GPU SAM. */
+ * .vcf input, sharded and multi-GPU SAM. */
 int dq_sam_open_memory(dq_ctx* ctx, const uint8_t* text, int64_t len);
 int dq_sam_open_path(dq_ctx* ctx, const char* path);
 int dq_sam_run(dq_ctx* ctx, dq_stats* stats); /* records stay in HBM */
 int dq_sam_read(dq_ctx* ctx, int32_t with_raw, dq_batch** out);
+
+/* ---- SAM output: SamSink.save's part file (row f8) --------------------------------------------
+ * Records into SAM lines as htsjdk 2.16 SAMTextWriter.getSAMString and TextTagCodec print them,
+ * each trimmed as Java's String.trim does (bytes <= 0x20 at both ends) and followed by LF.  The
+ * rules are DESIGN.md section 14; floats print as Float.toString does under the JDK 19+ contract.
+ * A malformed record gives DQ_EFORMAT and dq_last_error "record <k>: <what>": k = the 0-based
+ * index of the first offending record in input order; what = the first failing check of fields
+ * (the layout), QNAME, RNAME, CIGAR, RNEXT, QUAL, "tag XX" in that order.  A single line longer
+ * than 2^31-1 bytes gives DQ_EINVAL; offsets are 64-bit throughout.
+ * Out of scope: CRAM, one file per partition (AnySamSinkMultiple), a header re-encoded from a
+ * parsed SAMFileHeader, JDK 8's longer float texts, sharded and multi-GPU SAM output.
+ *
+ * dq_sam_write: header = the BAM header (dq_read_header's bytes; its references name RNAME/RNEXT).
+ * raw = n_records records back to back; raw_offset (may be NULL: the host walks the block_size
+ * chain) as dq_batch gives it.  n_records == 0 gives an empty output.  A chain that breaks at
+ * record k, or does not end exactly at raw_len (k = n_records), gives "record <k>: fields" unless
+ * an earlier record fails. */
+int dq_sam_write(dq_ctx* ctx, const uint8_t* header, int64_t header_len, const uint8_t* raw,
+                 int64_t raw_len, const int64_t* raw_offset, int64_t n_records, uint8_t** out,
+                 int64_t* out_len); /* *out: dq_free */
+/* Every record of the open whole file, once, in file order (a BAM context: the index-only run
+ * dq_write_bai makes; a SAM context: the records of dq_sam_run).  The text stays in HBM;
+ * dq_sam_write_fetch copies it out.  *ms (may be NULL) = device time of the size pass, the scan and
+ * the format pass.  A shard, a text (VCF) context, or no open file give DQ_EINVAL.  The context
+ * reads as before afterwards, as after dq_write_bai. */
+int dq_sam_write_resident(dq_ctx* ctx, int64_t* out_len, double* ms);
+int dq_sam_write_fetch(dq_ctx* ctx, uint8_t* host_out, int64_t cap);
 
 /* ---- BGZF compression: the write path -----------------------
  * Replaces htsjdk BlockCompressedOutputStream under HeaderlessBamOutputFormat.BamRecordWriter
@@ -449,7 +478,7 @@ void dq_free(void* p);
 /* Debug: the device bounds-checked build (`make -C disq_amd/csrc checked` ->
  * libdisq_gpu_checked.so, compiled with -DDQ_CHECKED).  Writes each kernel unit's failed-check
  * count << 32 | largest reported excess << 16 | site bits (K1/K3 kernels, K2 inflate, text
- * with the SAM unit folded in, deflate: 4 words) for the current
+ * with the SAM reader's and writer's units folded in, deflate: 4 words) for the current
  * device and resets them; returns 1 in the checked build, 0 in the product build (words all 0). */
 int dq_checked_report(uint64_t words[4]);
 
