@@ -73,6 +73,39 @@ class DqTextBatch(C.Structure):
                 ("part_digest", C.POINTER(C.c_uint64))]
 
 
+class DqVariantBatch(C.Structure):
+    _fields_ = [("n_variants", C.c_int64),
+                ("line_offset", C.POINTER(C.c_int64)),
+                ("line_len", C.POINTER(C.c_int32)),
+                ("hash", C.POINTER(C.c_uint64)),
+                ("contig", C.POINTER(C.c_int32)),
+                ("pos", C.POINTER(C.c_int32)),
+                ("end", C.POINTER(C.c_int32)),
+                ("flags", C.POINTER(C.c_uint32)),
+                ("qual", C.POINTER(C.c_double)),
+                ("col_end", C.POINTER(C.c_int32)),
+                ("n_alt", C.POINTER(C.c_int32)),
+                ("n_filter", C.POINTER(C.c_int32)),
+                ("n_info", C.POINTER(C.c_int32)),
+                ("n_sample_cols", C.POINTER(C.c_int32)),
+                ("data_offset", C.POINTER(C.c_int64)),
+                ("data", C.POINTER(C.c_uint8)),
+                ("n_bytes", C.c_int64),
+                ("n_partitions", C.c_int64),
+                ("part_offset", C.POINTER(C.c_int64)),
+                ("part_digest", C.POINTER(C.c_uint64)),
+                ("n_contigs", C.c_int32), ("reserved", C.c_int32),
+                ("contig_name_off", C.POINTER(C.c_int32)),
+                ("contig_names", C.POINTER(C.c_uint8)),
+                ("n_qual_host", C.c_int64)]
+
+
+# dq_vcf_read's export modes and dq_variant_batch.flags (include/disq_gpu.h)
+VCF_EXPORT_FIELDS, VCF_EXPORT_SITES, VCF_EXPORT_LINES = 0, 1, 2
+(VCF_HAS_ID, VCF_HAS_QUAL, VCF_UNFILTERED, VCF_PASS, VCF_INFO_END, VCF_HAS_GENOTYPES, VCF_SYMBOLIC,
+ VCF_REF_LOWER) = 1, 2, 4, 8, 16, 32, 64, 128
+
+
 class DqTraversal(C.Structure):
     _fields_ = [("ref", C.POINTER(C.c_int32)), ("start", C.POINTER(C.c_int32)),
                 ("end", C.POINTER(C.c_int32)), ("n", C.c_int64), ("has_intervals", C.c_int32),
@@ -115,7 +148,8 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_text_set_index", "dq_text_set_intervals", "dq_decode_file_multi",
            "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai",
            "dq_text_write_tbi", "dq_sam_open_memory", "dq_sam_open_path", "dq_sam_run",
-           "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch")
+           "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch",
+           "dq_vcf_run", "dq_vcf_read", "dq_variant_batch_free")
 
 _lib = None
 _lock = threading.Lock()
@@ -186,6 +220,9 @@ def lib():
         L.dq_text_set_intervals.argtypes = [vp, P(C.c_char_p), P(C.c_int32), P(C.c_int32),
                                             C.c_int64]
         L.dq_text_write_tbi.argtypes = [vp, P(P(C.c_uint8)), P(C.c_int64), P(C.c_double)]
+        L.dq_vcf_run.argtypes = [vp, P(DqStats)]
+        L.dq_vcf_read.argtypes = [vp, C.c_int32, P(P(DqVariantBatch))]
+        L.dq_variant_batch_free.argtypes = [P(DqVariantBatch)]
         L.dq_sam_open_memory.argtypes = [vp, vp, C.c_int64]
         L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
         L.dq_sam_run.argtypes = [vp, P(DqStats)]
@@ -519,6 +556,52 @@ class Context:
                     "part_digest": arr(b.part_digest, npart, np.uint64)}
         finally:
             lib().dq_text_batch_free(bp)
+
+    # ---- VCF site decode (dq_vcf_*) of an open text context
+    def vcf_run(self):
+        """Text run, then the validate and decode passes; the columns stay in HBM (dq_vcf_run).
+        ms_records is the device time of validate + decode."""
+        st = DqStats()
+        check(self._h, lib().dq_vcf_run(self._h, C.byref(st)))
+        return st
+
+    def vcf_read(self, mode=VCF_EXPORT_SITES):
+        """Every variant of every kept split, decoded on the device (dq_vcf_read): dict of numpy
+        arrays -- dq_text_read's line_offset, line_len, hash, part_offset and part_digest, the
+        columns contig, pos, end, flags, qual, col_end (n x 8), n_alt, n_filter, n_info and
+        n_sample_cols, data_offset and data (empty in FIELDS mode) -- plus contigs (the
+        ##contig IDs, bytes) and n_qual_host."""
+        bp = C.POINTER(DqVariantBatch)()
+        check(self._h, lib().dq_vcf_read(self._h, int(mode), C.byref(bp)))
+        try:
+            b = bp.contents
+            n, npart = b.n_variants, b.n_partitions
+
+            def arr(ptr, k, dt):
+                if not k or not ptr:
+                    return np.zeros(0, dt)
+                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
+            no = arr(b.contig_name_off, b.n_contigs + 1, np.int32)
+            names = arr(b.contig_names, int(no[-1]) if len(no) else 0, np.uint8).tobytes()
+            out = {"line_offset": arr(b.line_offset, n, np.int64),
+                   "line_len": arr(b.line_len, n, np.int32),
+                   "hash": arr(b.hash, n, np.uint64),
+                   "contig": arr(b.contig, n, np.int32), "pos": arr(b.pos, n, np.int32),
+                   "end": arr(b.end, n, np.int32), "flags": arr(b.flags, n, np.uint32),
+                   "qual": arr(b.qual, n, np.float64),
+                   "col_end": arr(b.col_end, 8 * n, np.int32).reshape(-1, 8),
+                   "n_alt": arr(b.n_alt, n, np.int32), "n_filter": arr(b.n_filter, n, np.int32),
+                   "n_info": arr(b.n_info, n, np.int32),
+                   "n_sample_cols": arr(b.n_sample_cols, n, np.int32),
+                   "data_offset": arr(b.data_offset, n + 1, np.int64),
+                   "data": arr(b.data, b.n_bytes, np.uint8),
+                   "part_offset": arr(b.part_offset, npart + 1, np.int64),
+                   "part_digest": arr(b.part_digest, npart, np.uint64),
+                   "contigs": [names[no[i]:no[i + 1]] for i in range(b.n_contigs)],
+                   "n_bytes": int(b.n_bytes), "n_qual_host": int(b.n_qual_host)}
+            return out
+        finally:
+            lib().dq_variant_batch_free(bp)
 
     def text_write_tbi(self) -> bytes:
         """htsjdk TabixIndexCreator over the open text file (dq_text_write_tbi): the decompressed

@@ -27,6 +27,7 @@
 #include "../../include/disq_gpu.h"
 #include "dq_internal.h"
 #include "dq_sam_core.h"
+#include "dq_vcf_core.h"
 
 using namespace dq;
 
@@ -119,7 +120,7 @@ struct Bai {
 struct dq_ctx {
   dq_opts o{};
   hipStream_t s = nullptr;
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[12] = {};  // 8..11: the VCF validate and decode passes
   // DQ_EXPORT_STREAMS=2: the export's device-to-pinned copies alternate between s and this second
   // stream (a second DMA engine); created on first use
   hipStream_t sx = nullptr;
@@ -151,6 +152,18 @@ struct dq_ctx {
   std::vector<int32_t> tiv_cid, tiv_start, tiv_end;  // per interval (contig id into tiv_contig)
   DevBuf t_ivnames, t_ivnoff, t_ivbeg, t_ivstart, t_ivend, t_ivmaxend;
   int64_t t_pruned = 0;                          // splits the index filter removed
+  // VCF site decode (dq_vcf_*) behind the text run: the header's sample flag and contig table (read
+  // once per open), the columns of the lines the text run kept, the undecided QUAL texts
+  int64_t text_gen = 0;             // counts the text runs that recomputed the line lists
+  int64_t vcf_gen = -1;             // the text run the columns belong to
+  bool vcf_hdr = false;
+  int32_t vcf_G = 0;
+  std::vector<std::string> vcf_contigs;
+  DevBuf v_ctg, v_scal, v_fix, v_contig, v_pos, v_end, v_flags, v_qual, v_colend, v_nalt, v_nfilter,
+      v_ninfo, v_nsample, v_sitelen;
+  dq::VcfContigs vcf_ctg{};
+  int64_t vcf_nqual_host = 0;
+  double vcf_ms = 0;
   // SAM text path (dq_sam_*): C holds the text itself; the records are encoded into sam_rec (their
   // offsets in rec_lin, rows in the f_* arrays), the built BAM header is hdr.  The line scan shares
   // the text path's terminator and keep / scan buffers (a context is in one mode at a time).
@@ -1282,6 +1295,7 @@ static int text_run(dq_ctx* ctx, int32_t drop_hash) {
   }
   ctx->have_text = true;
   ctx->text_drop = drop_hash;
+  ctx->text_gen++;
   return 0;
 }
 
@@ -2331,6 +2345,8 @@ static void reset_open(dq_ctx* ctx, int64_t len) {
   ctx->have_text = false;
   ctx->sam_mode = false;
   ctx->have_sam = false;
+  ctx->vcf_hdr = false;
+  ctx->vcf_gen = -1;
 }
 
 // Bytes [off, off + len) of an open file into C (plus the 4 KiB zero pad): read() into two pinned
@@ -3912,6 +3928,263 @@ int dq_text_read(dq_ctx* ctx, int32_t drop_header_lines, dq_text_batch** out) {
   return 0;
 }
 
+// ---- VCF site decode (row f9): VCFCodec.decode between the '#' filter and the overlap filter of
+// VcfSource.getVariants.  The text run leaves the line lists in HBM; the header's leading '#' lines
+// are read on the host, then the validate and decode passes of dq_vcf.hip.
+static int vcf_header(dq_ctx* ctx) {
+  if (ctx->vcf_hdr) return 0;
+  dqv::VcfHeader H;
+  std::vector<uint8_t> pre;
+  const int64_t ulen = ctx->ulen;
+  for (int64_t n = std::min<int64_t>(ulen, 1 << 20);; n = std::min<int64_t>(ulen, n * 8)) {
+    pre.resize((size_t)std::max<int64_t>(1, n));
+    if (n > 0) HIPCHK(hipMemcpy(pre.data(), ctx->U.p, (size_t)n, hipMemcpyDeviceToHost));
+    if (dqv::vcf_header_parse(pre.data(), n, n >= ulen, &H) == 0) break;
+    if (n >= ulen) break;
+  }
+  if (H.has_data && !H.has_chrom) RET(DQ_EFORMAT, "VCF header: no #CHROM line");
+  dqv::ContigTableHost R;
+  dqv::vcf_contig_table_build(H.contigs, &R);
+  // one buffer: hashes | name offsets | indices | name bytes
+  const size_t nr = H.contigs.size();
+  const size_t o_hash = 0, o_off = o_hash + 8 * nr, o_idx = o_off + 4 * (nr + 1),
+               o_names = o_idx + 4 * nr, bytes = o_names + R.names.size();
+  std::vector<uint8_t> buf(bytes + 8);
+  if (nr) {
+    memcpy(&buf[o_hash], R.hash.data(), 8 * nr);
+    memcpy(&buf[o_idx], R.idx.data(), 4 * nr);
+  }
+  memcpy(&buf[o_off], R.name_off.data(), 4 * (nr + 1));
+  memcpy(&buf[o_names], R.names.data(), R.names.size());
+  int rc;
+  if ((rc = ensure_all(ctx, ctx->v_ctg, buf.size()))) return rc;
+  HIPCHK(hipMemcpy(ctx->v_ctg.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  const uint8_t* d = ctx->v_ctg.as<uint8_t>();
+  ctx->vcf_ctg = VcfContigs{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
+                            (const int32_t*)(d + o_off), d + o_names, (int32_t)nr};
+  ctx->vcf_G = H.G ? 1 : 0;
+  ctx->vcf_contigs = H.contigs;
+  ctx->vcf_hdr = true;
+  return 0;
+}
+
+static VcfCols vcf_cols(dq_ctx* ctx) {
+  return VcfCols{ctx->v_contig.as<int32_t>(), ctx->v_pos.as<int32_t>(),     ctx->v_end.as<int32_t>(),
+                 ctx->v_flags.as<uint32_t>(), ctx->v_qual.as<double>(),     ctx->v_colend.as<int32_t>(),
+                 ctx->v_nalt.as<int32_t>(),   ctx->v_nfilter.as<int32_t>(), ctx->v_ninfo.as<int32_t>(),
+                 ctx->v_nsample.as<int32_t>(), ctx->v_sitelen.as<int32_t>()};
+}
+
+static int vcf_run(dq_ctx* ctx) {
+  if (ctx->sam_mode || !ctx->text_mode) RET(DQ_EINVAL, "not a text context (dq_text_open_*)");
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  int rc = text_run(ctx, 1);
+  if (rc) return rc;
+  if (ctx->vcf_gen == ctx->text_gen) return 0;
+  if ((rc = vcf_header(ctx))) return rc;
+  hipStream_t s = ctx->s;
+  const uint8_t* U = ctx->U.as<uint8_t>();
+  const int64_t ulen = ctx->ulen, total = ctx->t_total, n = ctx->t_nkept;
+  // ---- validate: every line of the kept splits the '#' filter keeps, before the overlap filter
+  if ((rc = ensure_all(ctx, ctx->v_scal, 64))) return rc;
+  unsigned long long* d_scal = ctx->v_scal.as<unsigned long long>();
+  const unsigned long long init[3] = {~0ull, 0, 0};  // first failing line | undecided | fix-ups
+  unsigned long long sc[2] = {~0ull, 0};
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(d_scal, init, sizeof init, hipMemcpyHostToDevice));
+  HIPCHK(hipEventRecord(ctx->ev[8], s));
+  launch_vcf_validate(U, ulen, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(), ctx->t_idx.as<int64_t>(),
+                      total, ctx->vcf_G, ctx->vcf_ctg, d_scal, s);
+  HIPCHK(hipEventRecord(ctx->ev[9], s));
+  HIPCHK(hipMemcpyAsync(sc, d_scal, 16, hipMemcpyDeviceToHost, s));  // one download: both words
+  HIPCHK(hipStreamSynchronize(s));
+  if (sc[0] != ~0ull) {
+    const int32_t st = (int32_t)(sc[0] & 0xff);
+    RET(DQ_EFORMAT, "VCF line " + std::to_string((long long)(sc[0] >> 8)) + ": " + dqv::vcf_status_name(st));
+  }
+  const int64_t nund = (int64_t)sc[1];
+  // ---- decode: the lines that survived the overlap filter and compaction
+  const size_t n1 = (size_t)std::max<int64_t>(1, n);
+  {
+    DevBuf* b4[] = {&ctx->v_contig, &ctx->v_pos,   &ctx->v_end,     &ctx->v_flags,  &ctx->v_nalt,
+                    &ctx->v_nfilter, &ctx->v_ninfo, &ctx->v_nsample, &ctx->v_sitelen};
+    for (auto* b : b4) if ((rc = ensure_all(ctx, *b, 4 * n1))) return rc;
+    if ((rc = ensure_all(ctx, ctx->v_qual, 8 * n1)) || (rc = ensure_all(ctx, ctx->v_colend, 32 * n1)) ||
+        (rc = ensure_all(ctx, ctx->v_fix, 24 * (size_t)std::max<int64_t>(1, nund))))
+      return rc;
+  }
+  HIPCHK(hipEventRecord(ctx->ev[10], s));
+  launch_vcf_decode(U, ulen, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(), total,
+                    ctx->t_kept.as<int64_t>(), n, ctx->vcf_G, ctx->vcf_ctg, vcf_cols(ctx),
+                    ctx->v_fix.as<int64_t>(), nund, d_scal + 2, s);
+  HIPCHK(hipEventRecord(ctx->ev[11], s));
+  unsigned long long cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if ((int64_t)cnt > nund) RET(DQ_EDEVICE, "VCF decode pass: more undecided QUAL texts than the validate pass counted");
+  // ---- QUAL fix-ups: the texts off the exact fast path, converted by strtod (normally none)
+  if (cnt > 0) {
+    std::vector<int64_t> ent(3 * (size_t)cnt);
+    HIPCHK(hipMemcpy(ent.data(), ctx->v_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
+    std::string txt;
+    for (size_t e = 0; e < (size_t)cnt; e++) {
+      const int64_t j = ent[3 * e], ta = ent[3 * e + 1], tn = ent[3 * e + 2];
+      if (j < 0 || j >= n || ta < 0 || tn <= 0 || ta + tn > ulen) RET(DQ_EDEVICE, "VCF decode pass: bad fix-up entry");
+      txt.assign((size_t)tn, '\0');
+      HIPCHK(hipMemcpy(&txt[0], U + ta, (size_t)tn, hipMemcpyDeviceToHost));
+      const double q = strtod(txt.c_str(), nullptr);
+      HIPCHK(hipMemcpy(ctx->v_qual.as<double>() + j, &q, 8, hipMemcpyHostToDevice));
+    }
+  }
+  ctx->vcf_nqual_host = (int64_t)cnt;
+  ctx->vcf_ms = (double)ev_ms(ctx->ev[8], ctx->ev[9]) + (double)ev_ms(ctx->ev[10], ctx->ev[11]);
+  ctx->vcf_gen = ctx->text_gen;
+  return 0;
+}
+
+int dq_vcf_run(dq_ctx* ctx, dq_stats* stats) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  if (ctx->sam_mode || !ctx->text_mode) RET(DQ_EINVAL, "not a text context (dq_text_open_*)");
+  // a re-run times the whole pipeline again
+  ctx->have_pipeline = false;
+  ctx->have_text = false;
+  int rc = vcf_run(ctx);
+  if (rc) return rc;
+  if (stats) {
+    *stats = ctx->stats;
+    stats->ms_plan += stats->ms_records;  // the text run's values, hashes and digests
+    stats->ms_records = ctx->vcf_ms;      // validate + decode
+    stats->ms_total += ctx->vcf_ms;
+  }
+  return 0;
+}
+
+int dq_vcf_read(dq_ctx* ctx, int32_t mode, dq_variant_batch** out) {
+  if (!ctx || !out) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  if (mode != DQ_VCF_EXPORT_FIELDS && mode != DQ_VCF_EXPORT_SITES && mode != DQ_VCF_EXPORT_LINES)
+    RET(DQ_EINVAL, "dq_vcf_read: unknown export mode");
+  int rc = vcf_run(ctx);
+  if (rc) return rc;
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
+  const size_t n1 = (size_t)std::max<int64_t>(1, n);
+  DevBuf o_start, o_len, o_hash, o_off, o_data, tmp;
+  HIPCHK(o_start.ensure(8 * n1));
+  HIPCHK(o_len.ensure(4 * n1));
+  HIPCHK(o_hash.ensure(8 * n1));
+  HIPCHK(o_off.ensure(8 * (n1 + 1)));
+  HIPCHK(tmp.ensure(sizeof(int64_t) * (size_t)(4 * ((int64_t)n1 / 1024 + 1) + 4096)));
+  launch_text_export(ctx->t_kept.as<int64_t>(), n, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(),
+                     ctx->t_hash.as<uint64_t>(), o_start.as<int64_t>(), o_len.as<int32_t>(),
+                     o_hash.as<uint64_t>(), s);
+  int64_t nbytes = 0;
+  if (mode != DQ_VCF_EXPORT_FIELDS && n > 0) {
+    const int32_t* lens = mode == DQ_VCF_EXPORT_SITES ? ctx->v_sitelen.as<int32_t>() : o_len.as<int32_t>();
+    launch_exclusive_scan_i32(lens, o_off.as<int64_t>(), n, tmp.as<int64_t>(), s);
+    if ((rc = get_i64(ctx, o_off.as<int64_t>() + n, &nbytes))) return rc;
+    if (nbytes < 0) RET(DQ_EDEVICE, "dq_vcf_read: bad byte total");
+    HIPCHK(o_data.ensure((size_t)std::max<int64_t>(1, nbytes)));
+    launch_vcf_gather(ctx->U.as<uint8_t>(), ctx->ulen, o_start.as<int64_t>(), lens, o_off.as<int64_t>(), n,
+                      o_data.as<uint8_t>(), s);
+  }
+  dq_variant_batch* b = (dq_variant_batch*)calloc(1, sizeof(dq_variant_batch));
+  if (!b) return DQ_ENOMEM;
+  const bool with_data = mode != DQ_VCF_EXPORT_FIELDS;
+  const size_t nc = ctx->vcf_contigs.size();
+  size_t name_bytes = 0;
+  for (const std::string& c : ctx->vcf_contigs) name_bytes += c.size();
+  b->n_variants = n;
+  b->n_partitions = nsplit;
+  b->line_offset = (int64_t*)malloc(8 * n1);
+  b->line_len = (int32_t*)malloc(4 * n1);
+  b->hash = (uint64_t*)malloc(8 * n1);
+  int32_t** c4[] = {&b->contig, &b->pos, &b->end, (int32_t**)&b->flags, &b->n_alt, &b->n_filter,
+                    &b->n_info, &b->n_sample_cols};
+  const DevBuf* d4[] = {&ctx->v_contig, &ctx->v_pos, &ctx->v_end, &ctx->v_flags, &ctx->v_nalt,
+                        &ctx->v_nfilter, &ctx->v_ninfo, &ctx->v_nsample};
+  bool ok = b->line_offset && b->line_len && b->hash;
+  for (auto** c : c4) ok = (*c = (int32_t*)malloc(4 * n1)) != nullptr && ok;
+  b->qual = (double*)malloc(8 * n1);
+  b->col_end = (int32_t*)malloc(32 * n1);
+  b->data_offset = (int64_t*)calloc(n1 + 1, 8);
+  b->data = with_data ? (uint8_t*)malloc((size_t)std::max<int64_t>(1, nbytes)) : nullptr;
+  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
+  b->part_digest = (uint64_t*)malloc(8 * (size_t)std::max<int64_t>(1, nsplit));
+  b->contig_name_off = (int32_t*)malloc(4 * (nc + 1));
+  b->contig_names = (uint8_t*)malloc(std::max<size_t>(1, name_bytes));
+  ok = ok && b->qual && b->col_end && b->data_offset && (b->data || !with_data) && b->part_offset &&
+       b->part_digest && b->contig_name_off && b->contig_names;
+  if (!ok) {
+    dq_variant_batch_free(b);
+    return DQ_ENOMEM;
+  }
+#define VCF_D2H(dst, src, bytes)                                                       \
+  do {                                                                                 \
+    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {     \
+      dq_variant_batch_free(b);                                                        \
+      RET(DQ_EDEVICE, "dq_vcf_read: device to host copy failed");                      \
+    }                                                                                  \
+  } while (0)
+  if (n > 0) {
+    VCF_D2H(b->line_offset, o_start.p, 8 * (size_t)n);
+    VCF_D2H(b->line_len, o_len.p, 4 * (size_t)n);
+    VCF_D2H(b->hash, o_hash.p, 8 * (size_t)n);
+    for (size_t i = 0; i < 8; i++) VCF_D2H(*c4[i], d4[i]->p, 4 * (size_t)n);
+    VCF_D2H(b->qual, ctx->v_qual.p, 8 * (size_t)n);
+    VCF_D2H(b->col_end, ctx->v_colend.p, 32 * (size_t)n);
+    if (with_data) VCF_D2H(b->data_offset, o_off.p, 8 * (size_t)(n + 1));
+  }
+  if (nbytes > 0) VCF_D2H(b->data, o_data.p, (size_t)nbytes);
+#undef VCF_D2H
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    dq_variant_batch_free(b);
+    RET(DQ_EDEVICE, "dq_vcf_read: device to host copy failed");
+  }
+  b->n_bytes = nbytes;
+  for (int64_t i = 0; i < nsplit; i++) {
+    b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
+    b->part_digest[i] = ctx->parts_h[(size_t)i].digest;
+  }
+  b->part_offset[nsplit] = n;
+  b->n_contigs = (int32_t)nc;
+  b->contig_name_off[0] = 0;
+  for (size_t r = 0; r < nc; r++) {
+    const std::string& c = ctx->vcf_contigs[r];
+    memcpy(b->contig_names + b->contig_name_off[r], c.data(), c.size());
+    b->contig_name_off[r + 1] = b->contig_name_off[r] + (int32_t)c.size();
+  }
+  b->n_qual_host = ctx->vcf_nqual_host;
+  *out = b;
+  return 0;
+}
+
+void dq_variant_batch_free(dq_variant_batch* b) {
+  if (!b) return;
+  free(b->line_offset);
+  free(b->line_len);
+  free(b->hash);
+  free(b->contig);
+  free(b->pos);
+  free(b->end);
+  free(b->flags);
+  free(b->qual);
+  free(b->col_end);
+  free(b->n_alt);
+  free(b->n_filter);
+  free(b->n_info);
+  free(b->n_sample_cols);
+  free(b->data_offset);
+  free(b->data);
+  free(b->part_offset);
+  free(b->part_digest);
+  free(b->contig_name_off);
+  free(b->contig_names);
+  free(b);
+}
+
 // TabixIndexCreator / BinningIndexBuilder (DESIGN.md "Building the .tbi"): data lines, their keys
 // and runs on the device (dq_text.hip), then the .bai kernels over the same key / voff / endp / pos
 // arrays; the host names the contigs, orders the bin headers and serialises.
@@ -4274,8 +4547,8 @@ int dq_checked_report(uint64_t words[4]) {
       words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
     }
   }
-  {  // and so does the SAM writer's unit
-    const uint64_t a = words[2], b = dq::dq_chk_take_samw();
+  for (int u = 0; u < 2; u++) {  // and so do the SAM writer's unit and the VCF decode's
+    const uint64_t a = words[2], b = u ? dq::dq_chk_take_vcf() : dq::dq_chk_take_samw();
     if (a == ~0ull || b == ~0ull) {
       words[2] = ~0ull;
     } else {

@@ -47,6 +47,8 @@ enum : int {
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
   CHK_SAM = 15,      // SAM read and write (dq_sam.hip, dq_samw.hip share the bit): a line, size,
                      //     record-byte, line-byte or fix-up slot
+  CHK_VCF = 15,      // VCF site decode (dq_vcf.hip shares the bit): a line, column row, fix-up slot or
+                     //     site byte
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -423,6 +425,44 @@ void launch_sam_encode(const uint8_t* T, const int64_t* lstart, const int64_t* v
                        const int64_t* roff, const int32_t* size, uint8_t* rec, RecSoA soa,
                        int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt, hipStream_t s);
 
+// ------------------------------------------------------------------ VCF site decode (dq_vcf.hip)
+struct VcfContigs {        // the ##contig IDs: hashes sorted ascending (ties by index), see dq_vcf_core.h
+  const uint64_t* hash;
+  const int32_t* idx;
+  const int32_t* name_off;  // n + 1 offsets into names, by contig index
+  const uint8_t* names;
+  int32_t n;
+};
+struct VcfCols {           // the columns of dq_variant_batch, one row per variant
+  int32_t* contig;
+  int32_t* pos;
+  int32_t* end;
+  uint32_t* flags;
+  double* qual;
+  int32_t* col_end;        // 8 per variant
+  int32_t* n_alt;
+  int32_t* n_filter;
+  int32_t* n_info;
+  int32_t* n_sample_cols;
+  int32_t* site_len;       // col_end[8 j + 7] again, contiguous for the scan of the SITES export
+};
+// Validate pass over the n lines of the text path's list (value start / length, lidx[t] = the
+// line's index in the file's line table); '#' lines are skipped.  scal[0] (all ones) takes the
+// smallest (line index << 8 | error class), scal[1] (zero) the undecided QUAL texts.
+void launch_vcf_validate(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
+                         const int64_t* lidx, int64_t n, int32_t G, VcfContigs ctg,
+                         unsigned long long* scal, hipStream_t s);
+// Decode pass over the n kept lines (kept[j] = entry of the list of `total` lines): the columns;
+// undecided QUAL texts appended to fix (3 words each: variant, text offset in U, text length),
+// counted in fix_cnt.
+void launch_vcf_decode(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
+                       int64_t total, const int64_t* kept, int64_t n, int32_t G, VcfContigs ctg,
+                       VcfCols out, int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt,
+                       hipStream_t s);
+// out[out_off[j] ...] = U[start[j], start[j] + len[j]) for the n variants (out_off[n] = total bytes)
+void launch_vcf_gather(const uint8_t* U, int64_t ulen, const int64_t* start, const int32_t* len,
+                       const int64_t* out_off, int64_t n, uint8_t* out, hipStream_t s);
+
 // ------------------------------------------------------------------ SAM writer (dq_samw.hip)
 struct SamwRefs {           // the header's reference names by index, see dq_samw_core.h
   const int32_t* name_off;  // n + 1 offsets into names
@@ -445,6 +485,7 @@ void launch_samw_format(const uint8_t* raw, int64_t raw_len, const int64_t* off,
 // DQ_CHECKED: each kernel unit's check words (count << 32 | site bits), read and reset
 uint64_t dq_chk_take_sam();
 uint64_t dq_chk_take_samw();
+uint64_t dq_chk_take_vcf();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

@@ -361,6 +361,46 @@ class VariantsPartition(list):
     """The variant lines of one Spark partition (bytes, terminators excluded)."""
 
 
+class VariantSite:
+    """One decoded variant (read(decode=True)): the site fields htsjdk's VCFCodec.decode computes
+    eagerly, built from dq_vcf_read's columns and the variant's site bytes.  contig is the CHROM
+    text, start and end are 1-based and closed, id is None for ".", alts is a list of bytes, qual
+    the QUAL text's value or None, filters None (unfiltered), an empty set (PASS) or the set of
+    filter names, info the INFO column's bytes."""
+    __slots__ = ("contig", "start", "end", "id", "ref", "alts", "qual", "filters", "info")
+
+    def __init__(self, contig, start, end, id, ref, alts, qual, filters, info):
+        self.contig, self.start, self.end, self.id, self.ref = contig, start, end, id, ref
+        self.alts, self.qual, self.filters, self.info = alts, qual, filters, info
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, VariantSite) and self._key() == other._key()
+
+    def __repr__(self):
+        return "VariantSite(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+
+def variant_sites(b):
+    """The VariantSite rows of a SITES (or LINES) batch of Context.vcf_read, per partition."""
+    d, do, ce, fl = b["data"], b["data_offset"], b["col_end"], b["flags"]
+    rows = []
+    for k in range(len(fl)):
+        e = [int(x) for x in ce[k]]
+        site = bytes(d[do[k]:do[k] + e[7]])
+        col = [site[(e[c - 1] + 1 if c else 0):e[c]] for c in range(8)]
+        f = int(fl[k])
+        filters = None if f & _lib.VCF_UNFILTERED else set() if f & _lib.VCF_PASS else set(col[6].split(b";"))
+        rows.append(VariantSite(col[0], int(b["pos"][k]), int(b["end"][k]),
+                                col[2] if f & _lib.VCF_HAS_ID else None, col[3],
+                                col[4].split(b",") if int(b["n_alt"][k]) else [],
+                                float(b["qual"][k]) if f & _lib.VCF_HAS_QUAL else None, filters, col[7]))
+    po = b["part_offset"]
+    return [VariantsPartition(rows[po[p]:po[p + 1]]) for p in range(len(po) - 1)]
+
+
 class VariantsRDD:
     def __init__(self, partitions):
         self.partitions = partitions
@@ -392,7 +432,8 @@ class HtsjdkVariantsRdd:
 class HtsjdkVariantsRddStorage:
     """Builder + read() of Disq's variants entry point (D/HtsjdkVariantsRddStorage.java:25-83,
     VcfSource.getVariants D/impl/formats/vcf/VcfSource.java:88-113) for BGZF-compressed VCF on the
-    GPU text path.  Lines are returned undecoded: VCFCodec record parsing stays with the caller."""
+    GPU text path.  Lines are returned undecoded by default; read(decode=True) decodes them on the
+    device (dq_vcf_read) into VariantSite rows."""
 
     def __init__(self, device: int = 0):
         self._split_size = 0
@@ -406,7 +447,10 @@ class HtsjdkVariantsRddStorage:
         self._split_size = int(splitSize)
         return self
 
-    def read(self, path: str, intervals: Optional[Sequence[Interval]] = None) -> HtsjdkVariantsRdd:
+    def read(self, path: str, intervals: Optional[Sequence[Interval]] = None,
+             decode: bool = False) -> HtsjdkVariantsRdd:
+        """decode: each partition holds VariantSite rows (the device's VCFCodec.decode, SITES
+        export: only the first eight columns' bytes cross to the host) instead of line bytes."""
         if not (path.endswith(".gz") or path.endswith(".bgz")):
             raise ValueError(f"{path}: the GPU text path reads BGZF-compressed VCF (.vcf.gz/.vcf.bgz)")
         with _lib.Context(split_size=self._split_size, device=self._device) as ctx:
@@ -419,7 +463,9 @@ class HtsjdkVariantsRddStorage:
                     ctx.text_set_index(fh.read())
                 ctx.text_set_intervals([(iv.getContig(), iv.getStart(), iv.getEnd())
                                         for iv in intervals])
-            b = ctx.text_read(True)
+            b = ctx.vcf_read(_lib.VCF_EXPORT_SITES) if decode else ctx.text_read(True)
+        if decode:
+            return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(variant_sites(b)))
         d, do, ln, po = b["data"], b["data_offset"], b["line_len"], b["part_offset"]
         parts = [VariantsPartition(bytes(d[do[k]:do[k] + ln[k]]) for k in range(po[p], po[p + 1]))
                  for p in range(len(po) - 1)]

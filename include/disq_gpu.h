@@ -28,6 +28,8 @@
  *     (D/impl/formats/sam/SamSource.java:36-77)                             dq_sam_read
  *   SamSink.save's part file: SAMRecord.getSAMString, String.trim, a LF per read
  *     (D/impl/formats/sam/SamSink.java:37)                                  dq_sam_write
+ *   VCFCodec.decode of every data line, the step of VcfSource.getVariants between the '#'
+ *     filter and the overlap filter (D/impl/formats/vcf/VcfSource.java:113)    dq_vcf_read
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -349,7 +351,7 @@ int dq_debug_guess_all(dq_ctx* ctx, uint64_t* voffs, int64_t cap, int64_t* n);
  * LineRecordReader, as VcfSource.getVariants uses them (D/impl/formats/vcf/VcfSource.java:88-113).
  * A partition is one FileInputFormat split (same arithmetic as the BAM path); its lines are the
  * values LineRecordReader returns, terminators excluded; drop_header_lines drops the values
- * starting with '#' (VcfSource.java:108).  Parsing a line into a VariantContext is the caller's. */
+ * starting with '#' (VcfSource.java:108).  Parsing a line into a VariantContext is dq_vcf_read's. */
 typedef struct dq_text_batch {
   int64_t n_lines;
   int64_t* line_offset;   /* value offset in the file's decompressed stream */
@@ -391,6 +393,66 @@ void dq_text_batch_free(dq_text_batch* b);
  * library-allocated (dq_free); *ms (may be NULL) = device time of the index build alone, after
  * scan, inflate and the terminator scan. */
 int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms);
+
+/* ---- VCF site decode: VCFCodec.decode --------------------------
+ * Every data line of an open text context (dq_text_open_*; a set index and set intervals are
+ * honoured) decoded on the device into the site fields htsjdk's AbstractVCFCodec.parseVCFLine
+ * computes eagerly; genotypes stay text, as htsjdk's LazyGenotypesContext leaves them.  The rules
+ * are DESIGN.md section 15.  The variants are exactly the lines dq_text_read(ctx, 1, ...) returns:
+ * partitions, offsets, lengths, hashes and digests are the same.  The header is the stream's
+ * leading '#' lines: the ##contig IDs (contig indexes them, -1 for a CHROM that names none) and
+ * the #CHROM line, which decides whether lines carry genotype columns; data lines without a #CHROM
+ * line give DQ_EFORMAT "VCF header: no #CHROM line".  Every line of the kept splits that does not
+ * start with '#' is validated, before the interval filter (Disq decodes, then filters): a malformed
+ * one gives DQ_EFORMAT and dq_last_error "VCF line <k>: <what>", k the 0-based index of the first
+ * offender among all the file's lines, what one of fields, CHROM, POS, ID, REF, ALT, QUAL, FILTER,
+ * INFO.  A BAM or SAM context, no open file or an unknown mode gives DQ_EINVAL.  The dq_text_*
+ * calls work as before on the same context afterwards. */
+#define DQ_VCF_EXPORT_FIELDS 0   /* columns only, data = NULL */
+#define DQ_VCF_EXPORT_SITES  1   /* + each variant's first col_end[7] bytes (columns 1-8) */
+#define DQ_VCF_EXPORT_LINES  2   /* + each variant's whole value, as dq_text_read gives it */
+/* flags */
+#define DQ_VCF_HAS_ID 1
+#define DQ_VCF_HAS_QUAL 2
+#define DQ_VCF_UNFILTERED 4      /* FILTER "." */
+#define DQ_VCF_PASS 8
+#define DQ_VCF_INFO_END 16       /* end came from INFO END */
+#define DQ_VCF_HAS_GENOTYPES 32  /* a 9th column exists */
+#define DQ_VCF_SYMBOLIC 64       /* some ALT is symbolic or a breakend */
+#define DQ_VCF_REF_LOWER 128     /* REF holds a lower-case base (htsjdk upper-cases it) */
+typedef struct dq_variant_batch {
+  int64_t n_variants;
+  int64_t* line_offset;    /* exactly dq_text_batch's line_offset, line_len and hash */
+  int32_t* line_len;
+  uint64_t* hash;
+  int32_t* contig;         /* index of the ##contig line whose ID is CHROM, or -1 */
+  int32_t* pos;            /* POS */
+  int32_t* end;            /* the INFO END value, or POS + len(REF) - 1 */
+  uint32_t* flags;         /* DQ_VCF_* */
+  double* qual;            /* the QUAL text's binary64 (0 without DQ_VCF_HAS_QUAL) */
+  int32_t* col_end;        /* 8 per variant: column c = [c ? col_end[8k+c-1]+1 : 0, col_end[8k+c]) */
+  int32_t* n_alt;
+  int32_t* n_filter;       /* 0 for "." and PASS */
+  int32_t* n_info;         /* 0 for "." */
+  int32_t* n_sample_cols;  /* columns after FORMAT */
+  int64_t* data_offset;    /* variant k's bytes = data[data_offset[k] ...) (SITES, LINES) */
+  uint8_t* data;
+  int64_t n_bytes;
+  int64_t n_partitions;
+  int64_t* part_offset;    /* as dq_text_read(ctx, 1, ...) */
+  uint64_t* part_digest;
+  int32_t n_contigs;
+  int32_t reserved;
+  int32_t* contig_name_off; /* n_contigs + 1 offsets into contig_names */
+  uint8_t* contig_names;
+  int64_t n_qual_host;     /* QUAL texts off the device's exact path, converted by the host's strtod */
+} dq_variant_batch;
+/* The text run, then validate and decode; the columns stay in HBM.  stats: dq_text_run's, with
+ * ms_records = the device time of validate + decode (the text run's own ms_records, its values,
+ * hashes and digests, is added to ms_plan) and ms_total including it. */
+int dq_vcf_run(dq_ctx* ctx, dq_stats* stats);
+int dq_vcf_read(dq_ctx* ctx, int32_t mode, dq_variant_batch** out);
+void dq_variant_batch_free(dq_variant_batch* b);
 
 /* ---- SAM text: SamSource.getReads -----------------------------
  * An uncompressed SAM file read as Disq reads it (D/impl/formats/sam/SamSource.java:36-77): Hadoop
