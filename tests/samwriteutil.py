@@ -4,6 +4,7 @@ String.trim, as SamSink.save maps every read (D/impl/formats/sam/SamSink.java:37
 code with the library.  Floats are Java's Float.toString (the JDK 19+ contract) worked out with
 fractions.Fraction; samutil is used for nothing here, its own converter is careless about floats,
 trim and malformed records."""
+import functools
 import struct
 from fractions import Fraction
 
@@ -65,8 +66,9 @@ def float_decimal(bits: int):
     return best[0], n, best[1]
 
 
+@functools.lru_cache(maxsize=None)
 def float_text(bits: int) -> bytes:
-    """Float.toString of the binary32 with these bits."""
+    """Float.toString of the binary32 with these bits (worked out once per value)."""
     bits &= 0xffffffff
     exp, frac = (bits >> 23) & 0xff, bits & 0x7fffff
     sign = b"-" if bits >> 31 else b""

@@ -2,20 +2,18 @@
 on the CPU through tools/sam_core_check.cpp and compared with the oracle tests/samutil.py: records
 byte for byte, error classes by name, floats bit for bit (an undecided float is allowed, a wrong
 one is not)."""
-import decimal
-import fractions
 import os
-import random
 import struct
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 import bamutil as B
+import floatcases as F
 import samcases as K
 import samutil as S
+from floatref import exact_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,43 +99,12 @@ def test_one_line_per_error_class(tool, tmp_path):
                     "TLEN", "SEQ", "QUAL", "tag"}
 
 
-def _sig_digits(t):
-    m = t.lstrip("+-").lower().split("e")[0].replace(".", "").lstrip("0")
-    return len(m)
-
-
 def test_floats_bit_for_bit(tool, tmp_path):
-    rng = random.Random(20240607)
-    pats = []
-    while len(pats) < 20000:
-        b = rng.getrandbits(32)
-        if (b >> 23) & 0xff != 0xff:
-            pats.append(b)
-    texts = []
-    f32 = np.array(pats, np.uint32).view(np.float32)
-    for x in f32:
-        texts.append(repr(float(x)))                # shortest repr of the binary32 as a double
-        texts.append("%.9g" % float(x))
-        texts.append(np.format_float_scientific(x, unique=True, trim="-"))  # shortest for binary32 itself
-    # exact decimal midpoints between a float and its successor
-    decimal.getcontext().prec = 400
-    for b in pats[:2000]:
-        b &= 0x7fffffff
-        if b >= 0x7f7fffff:
-            continue
-        lo, hi = (fractions.Fraction(float(np.array([v], np.uint32).view(np.float32)[0]))
-                  for v in (b, b + 1))
-        mid = (lo + hi) / 2
-        texts.append(format(decimal.Decimal(mid.numerator) / decimal.Decimal(mid.denominator), "f"))
-    texts += ["7.038531e-26", "0", "-0.0", "1e-46", "1e39", ".5", "+1e+0", "-1e39", "1e-45", "7e-46",
-              "0." + "0" * 30 + "123", "0" * 30 + "1.5", "1.234567890123456789012345",
-              "3.4028235e38", "3.4028236e38", "1.17549435e-38", "1e99999999999999999999",
-              "1e-99999999999999999999", "0e99999", "123456789012345678901234567890",
-              "16777217", "16777219", "9007199791611905", "1.00000017881393432617187500",
-              "1.00000017881393421514957253748434595763683319091796875"]
-    bad = ["", "+", ".", "5.", "1.e5", "e5", "1e", "1e+", "nan", "inf", "0x1p3", "1 ", " 1", "1f", "--1",
-           "1.5.2", "1e5.0", "1,5", "+.e1"]
-    texts += bad
+    """Against the exact reference tests/floatref.py: libc's strtof is what the library's own
+    fix-up path calls."""
+    texts, bad = F.sam_float_texts(), F.SAM_BAD
+    ties = set(F.short_ties())
+    assert texts[-len(bad):] == bad and len(ties) > 3000
     src, dst = tmp_path / "f.txt", tmp_path / "f.out"
     src.write_bytes(b"".join(t.encode() + b"\n" for t in texts))
     subprocess.run([tool, "floats", str(src), str(dst)], check=True)
@@ -149,11 +116,13 @@ def test_floats_bit_for_bit(tool, tmp_path):
         assert (g == "BAD") == (not ok), (t, g)
         if not ok:
             continue
-        if _sig_digits(t) <= 17:
+        if F.sig_digits(t) <= 17:
             short += 1
             undecided_short += g == "UNDECIDED"
+        if t in ties:                              # the tie rule decides every one of them itself
+            assert g != "UNDECIDED", t
         if g != "UNDECIDED":
-            assert g == "OK " + S.pack_float(t.encode())[::-1].hex(), (t, g)
+            assert g == "OK %08x" % exact_bits(t.encode()), (t, g)
     assert all(g == "BAD" for g in got[-len(bad):])
     assert got[texts.index("7.038531e-26")] == "OK 15ae43fd"
     assert short > 60000 and undecided_short <= short // 100, (undecided_short, short)

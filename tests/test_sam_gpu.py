@@ -3,6 +3,7 @@ tests/samutil.py -- record bytes from sam_line_to_bam_record, partition membersh
 plain_text_partitions (Hadoop's rule for an uncompressed split), hashes and digests from
 oracle.record_hash / stream_digest -- and against the BAM path reading the same reads."""
 import os
+import re
 import struct
 
 import numpy as np
@@ -12,19 +13,31 @@ from disq_amd import _lib
 from disq_amd.storage import (HtsjdkReadsRddStorage, HtsjdkReadsTraversalParameters, Interval)
 from oracle import oracle as O
 import bamutil as B
+import floatcases as F
 import samcases as K
 import samutil as S
+from floatref import exact_bytes
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SAM_LONG = int(re.search(r"SAM_LONG = (\d+);", open(os.path.join(ROOT, "disq_amd", "csrc", "dq_sam.hip")).read()).group(1))
 
 FIELDS = ("block_size", "ref_id", "pos", "l_read_name", "mapq", "bin", "n_cigar", "flag", "l_seq",
           "next_ref_id", "next_pos", "tlen")
 
 
-def oracle_parts(text, splits):
-    """Per split the [(line offset, record bytes)] of its lines that do not start with '@'."""
+def oracle_parts(text, splits, memo=None):
+    """Per split the [(line offset, record bytes)] of its lines that do not start with '@'.  memo:
+    a dict that keeps every line's record for the next call on the same text."""
     names = S.sam_header_to_bam(text)[1]
-    return [[(o, S.sam_line_to_bam_record(v, names)) for o, v in part if not v.startswith(b"@")]
+    memo = {} if memo is None else memo
+
+    def rec(o, v):
+        if o not in memo:
+            memo[o] = S.sam_line_to_bam_record(v, names)
+        return memo[o]
+    return [[(o, rec(o, v)) for o, v in part if not v.startswith(b"@")]
             for part in S.plain_text_partitions(text, splits)]
 
 
@@ -33,9 +46,9 @@ def records_of(b):
     return [bytes(raw[int(ro[i]):int(ro[i]) + 4 + int(bs[i])]) for i in range(len(bs))]
 
 
-def assert_sam_parity(text, split=0, nio=False):
+def assert_sam_parity(text, split=0, nio=False, memo=None):
     splits = O.path_splits(len(text), split, nio)
-    want = oracle_parts(text, splits)
+    want = oracle_parts(text, splits, memo)
     with _lib.Context(split_size=split, use_nio=nio) as c:
         c.sam_open_bytes(text)
         _, hdr = c.header()
@@ -291,3 +304,131 @@ def test_export_modes_and_arena(golden):
         del a
         assert records_of(c.sam_read(with_raw="lean") | {"raw_offset": full["raw_offset"],
                                                           "block_size": full["block_size"]}) == recs
+
+
+# ---- float texts at the CPU tests' scale: the device's own conversion, and the host's fix-ups
+@pytest.fixture(scope="module")
+def float_texts():
+    """(decided, hard, exact): the texts of floatcases.sam_float_texts() the SAM rule accepts, with
+    at most 19 significant digits (sam_parse_float takes them all in) and with more (it leaves
+    them to the host, whatever their value), and every text's exact binary32 bytes."""
+    texts = [t.encode() for t in F.sam_float_texts()]
+    texts = [t for t in texts if S.FLOAT_RE.match(t)]
+    decided = [t for t in texts if F.sig_digits(t.decode()) <= 19]
+    hard = [t for t in texts if F.sig_digits(t.decode()) > 19]
+    assert len(decided) > 65000 and len(hard) > 1500
+    assert set(t.encode() for t in F.short_ties()) <= set(decided)
+    return decided, hard, {t: exact_bytes(t) for t in set(texts)}
+
+
+def array_line(texts, qname=b"q"):
+    return K.line(qname=qname, flag=4, rname=b"*", pos=0, mapq=0, cigar=b"*", seq=b"*", qual=b"*",
+                  tags=(b"XB:B:f," + b",".join(texts),))
+
+
+def array_lines(texts, per_line, max_len=None, min_len=None):
+    """[(line, its texts)]: B:f arrays of per_line texts each.  max_len: a line is closed early
+    where one more text would take it past max_len bytes.  min_len: a last line that is not longer
+    than min_len gives its texts to the line before it."""
+    groups, cur = [], []
+    for t in texts:
+        if len(cur) == per_line or (max_len and cur and len(array_line(cur + [t], b"a%d" % len(groups))) > max_len):
+            groups.append(cur)
+            cur = []
+        cur.append(t)
+    if cur:
+        if min_len and groups and len(array_line(cur)) <= min_len:
+            groups[-1] += cur
+        else:
+            groups.append(cur)
+    return [(array_line(g, b"a%d" % i), g) for i, g in enumerate(groups)]
+
+
+def assert_float_parity(lines, exact, splits):
+    """assert_sam_parity of HEADER + the (line, float texts) pairs at every split; the expected
+    records' float bytes -- the last 4 per text of each record -- are the exact reference's, so
+    the oracle's strtof is pinned to it."""
+    text = K.HEADER + b"".join(l + b"\n" for l, _ in lines)
+    memo = {}
+    for split in splits:
+        b, st = assert_sam_parity(text, split, memo=memo)
+        assert st.n_records == len(lines)
+    for (o, v), (l, ts) in zip([x for x in S.text_lines(text) if not x[1].startswith(b"@")], lines):
+        assert v == l
+        if ts:
+            assert memo[o][-4 * len(ts):] == b"".join(exact[t] for t in ts), l[:60]
+    return b, text
+
+
+def test_float_texts_thread_path(float_texts):
+    """Every text the device decides itself, in lines of up to SAM_LONG bytes: a thread per line."""
+    decided, _, exact = float_texts
+    lines = array_lines(decided, 100, max_len=SAM_LONG)
+    singles = decided[::len(decided) // 2000][:2000]
+    assert len(singles) == 2000
+    lines += [(K.BASE + b"\tXF:f:" + t, [t]) for t in singles]
+    assert max(len(l) for l, _ in lines) <= SAM_LONG
+    assert sum(len(ts) == 100 for _, ts in lines) > len(decided) // 200     # most arrays are full
+    b, _ = assert_float_parity(lines, exact, (0, 65536))
+    assert len(b["part_offset"]) - 1 > 10
+
+
+def test_float_texts_wave_path(float_texts):
+    """The same texts in lines past SAM_LONG -- a wave per line, lane 0 walks the tags -- between
+    short lines."""
+    decided, _, exact = float_texts
+    long_lines = array_lines(decided, 1000, min_len=SAM_LONG)
+    assert min(len(l) for l, _ in long_lines) > SAM_LONG and len(long_lines) >= len(decided) // 1000
+    short = [(l, []) for l in _lines24()]
+    lines = []
+    for i, ll in enumerate(long_lines):
+        lines += [short[i % 24], ll, (K.BASE + b"\tXF:f:" + decided[i * 997], [decided[i * 997]])]
+    assert_float_parity(lines, exact, (0, 65536))
+
+
+def _fixup_lines(decided, hard):
+    """Long lines of a hundred undecided texts each, a decided one after every undecided one, and
+    short lines of (up to) ten undecided texts, in turn."""
+    lines, i, k = [], 0, 0
+    while i < len(hard):
+        ts = []
+        for t in hard[i:i + 100]:
+            ts += [t, decided[k % len(decided)]]
+            k += 7
+        while len(array_line(ts)) <= SAM_LONG:      # the last, shorter group
+            ts.append(decided[k % len(decided)])
+            k += 7
+        lines.append((array_line(ts, b"long%d" % len(lines)), ts))
+        i += 100
+        ts = []
+        for t in hard[i:i + 10]:
+            if ts and len(array_line(ts + [t])) > SAM_LONG:
+                break
+            ts.append(t)
+        if ts:
+            lines.append((array_line(ts, b"short%d" % len(lines)), ts))
+            i += len(ts)
+    return lines
+
+
+def test_float_fixups_at_scale(float_texts):
+    """Some 1,600 texts the host converts, in both encode kernels' fix-up lists: each value lands
+    in its own 4-byte slot before the hash pass (assert_sam_parity compares the record bytes and
+    the hash of every record), in partitions of 4096 bytes, some of which start inside a long line."""
+    decided, hard, exact = float_texts
+    lines = _fixup_lines(decided, hard)
+    kinds = [len(l) > SAM_LONG for l, _ in lines]
+    assert kinds[:-1] == [i % 2 == 0 for i in range(len(lines) - 1)] and sum(kinds) >= 15
+    hs = set(hard)
+    n_long = sum(sum(t in hs for t in ts) for (l, ts), k in zip(lines, kinds) if k)
+    n_short = sum(len(ts) for (l, ts), k in zip(lines, kinds) if not k)
+    assert n_long > 1000 and n_short > 100 and n_long + n_short == len(hard)
+    b, text = assert_float_parity(lines, exact, (0, 4096))
+    assert (np.diff(b["part_offset"]) == 0).any()           # splits in which no line starts
+    # an error behind undecided texts, in a long line that follows lines with undecided texts: the
+    # size pass reports it, and nothing of the fix-up counts gets in its way
+    ts = lines[2][1]
+    bad = array_line(ts[:9] + [b"1."] + ts[9:], b"bad")
+    assert len(bad) > SAM_LONG and all(t in hs for t in ts[:9:2])
+    broken = K.HEADER + b"".join(l + b"\n" for l, _ in lines[:6]) + bad + b"\n" + lines[6][0] + b"\n"
+    assert sam_error(broken).endswith("SAM line %d: tag XB" % (K.HEADER.count(b"\n") + 6))

@@ -175,15 +175,65 @@ def test_zero_and_one_record():
     check([W.make_record()])
 
 
+def _float_tag(name, v):
+    return name + b"Bf" + struct.pack("<i", len(v)) + struct.pack("<%dI" % len(v), *v)
+
+
+def float_array_records(vals, per_record):
+    """Unmapped records (what the SAM reader makes of their lines, bin included) with one B:f array
+    of per_record values each; a last group of fewer than half as many joins the one before it."""
+    groups = [vals[i:i + per_record] for i in range(0, len(vals), per_record)]
+    if len(groups) > 1 and 2 * len(groups[-1]) < per_record:
+        groups[-2:] = [groups[-2] + groups[-1]]
+    return [W.make_record(qname=b"f%d" % i, flag=4, ref=-1, pos=-1, mapq=0, cigar=(), seq=b"", l_seq=0, qual=b"",
+                          tags=_float_tag(b"XB", g)) for i, g in enumerate(groups)]
+
+
+def finite_floats(n_random):
+    """float_set(n_random) and the binade edges of both signs, the finite ones."""
+    edges = W.binade_edges()
+    return [b for b in W.float_set(n_random) + edges + [0x80000000 | b for b in edges] if (b >> 23) & 0xff != 0xff]
+
+
 def test_floats():
     edges = W.binade_edges()
     edges = edges + [0x80000000 | b for b in edges]
-    tag = lambda name, v: name + b"Bf" + struct.pack("<i", len(v)) + struct.pack("<%dI" % len(v), *v)
+    tag = _float_tag
     check([W.make_record(tags=tag(b"XA", edges[:900]) + tag(b"XB", edges[900:])),
            W.make_record(tags=tag(b"XC", edges[:100])), W.make_record(tags=tag(b"XD", []))])
     singles = (W.float_set(0) + edges)[:2000]
     assert len(singles) == 2000
     check([W.make_record(tags=b"XFf" + struct.pack("<I", b)) for b in singles])
+    # at scale, a hundred values a record (a thread per record) and a thousand (a wave per record);
+    # the oracle works out each value's text once (samwriteutil.float_text keeps its results)
+    vals = finite_floats(20000) + [0x7f800000, 0xff800000, 0x7fc00000]
+    assert len(vals) > 24000
+    with _lib.Context() as c:
+        for per, long in ((100, False), (1000, True)):
+            recs = float_array_records(vals, per)
+            assert all((len(r) > LONG) == long for r in recs) and len(recs) >= len(vals) // per
+            check(recs, ctx=c)
+
+
+def test_float_round_trip_on_device():
+    """Every finite value the writer prints is read back to itself by the SAM reader's own
+    conversion: the records and their hashes return unchanged, through the thread and the wave
+    path of both."""
+    from oracle import oracle as O
+    vals = finite_floats(20000)
+    assert len(vals) > 24000
+    for per in (100, 1000):
+        recs = float_array_records(vals, per)
+        raw = b"".join(recs)
+        with _lib.Context() as c:
+            text = c.sam_write(HDR, raw, offsets(recs))
+        lines = text.split(b"\n")[:-1]
+        assert len(lines) == len(recs) and all((len(l) > 2048) == (per == 1000) for l in lines)
+        with _lib.Context() as c:
+            c.sam_open_bytes(W.header_text(HDR) + text)
+            b = c.sam_read(with_raw=True)
+        assert bytes(b["raw"]) == raw
+        assert b["hash"].tolist() == [O.record_hash(r) for r in recs]
 
 
 def test_resident_bam(bam1):

@@ -4,14 +4,15 @@ column by column, error classes by name, QUAL values bit for bit (an undecided t
 wrong value is not)."""
 import gzip
 import os
-import random
 import struct
 import subprocess
 
 import pytest
 
+import floatcases as F
 import vcfcases as K
 import vcfutil as V
+from floatref import BINARY64, exact_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -102,31 +103,12 @@ def test_header_without_chrom_line(tool, tmp_path):
     assert dst.read_text() == "H nochrom\n"
 
 
-def _qual_texts():
-    rng = random.Random(20241019)
-    texts = []
-    while len(texts) < 60000:
-        x = struct.unpack("<d", struct.pack("<Q", rng.getrandbits(64)))[0]
-        if x != x or x in (float("inf"), float("-inf")):
-            continue
-        y = rng.uniform(-1e6, 1e6) if len(texts) % 2 else x   # QUAL-like magnitudes and any double
-        texts += ["%.2f" % y if abs(y) < 1e30 else "%.2f" % rng.uniform(0, 1e5), "%.6g" % y, "%.17g" % y]
-    return texts
-
-
-def _digits(t):
-    return len(t.lstrip("+-").lower().split("e")[0].replace(".", "").lstrip("0"))
-
-
 def test_quals_bit_for_bit(tool, tmp_path):
-    texts = _qual_texts()
-    assert len(texts) == 60000
-    extra = ["0", "-0", "-0.0", "5.", "1e22", "1e23", "1e-22", "1e-23", "9007199254740993", "123456789012345e7",
-             "0.000000000000000000000001", "100000000000000000000", "1e400", "1e-400", "4.9e-324", ".5",
-             "+.5e+1", "0e999", "1e-30", "123456789012345678", "000000000000000000001.50",
-             "8.98846567431158e307", "2.2250738585072011e-308", "1.7976931348623157e308"]
-    bad = ["", "+", ".", "e5", "1e", "1e+", "nan", "NaN", "inf", "Infinity", "0x1p3", "1 ", " 1", "1f", "1d", "--1",
-           "1.5.2", "1e5.0", "1,5", "+.e1", "1e5f"]
+    """Against the exact reference tests/floatref.py."""
+    texts = F.qual_texts()
+    edge = F.qual_edge_texts()
+    assert len(texts) == 60000 + len(edge) and texts[60000:] == edge and len(edge) == 1200
+    extra, bad = F.QUAL_EXTRA, F.QUAL_BAD
     texts = texts + extra + bad
     src, dst = tmp_path / "q.txt", tmp_path / "q.out"
     src.write_bytes(b"".join(t.encode() + b"\n" for t in texts))
@@ -141,12 +123,14 @@ def test_quals_bit_for_bit(tool, tmp_path):
             continue
         assert (g == "UNDECIDED") == (not V.qual_fast_path(t.encode())), (t, g)
         if g != "UNDECIDED":                       # never a wrong value
-            assert g == "OK %016x" % bits(float(t)), (t, g)
+            assert g == "OK %016x" % exact_bits(t.encode(), BINARY64), (t, g)
             decided += 1
-        if i < 60000 and i % 3 == 0 and _digits(t) <= 15:
+        if i < 60000 and i % 3 == 0 and F.sig_digits(t) <= 15:
             assert g != "UNDECIDED", t           # no %.2f text of up to 15 digits goes to the host
     assert all(g == "BAD" for g in got[-len(bad):])
     assert decided > 30000
+    # the 15-digit mantissas: decided at the decimal exponents +-21 and +-22, the host's at +-23
+    assert [g != "UNDECIDED" for g in got[60000:61200]] == [i // 200 < 4 for i in range(1200)]
 
 
 def test_runs_clean_under_the_sanitizers(tmp_path, golden):
@@ -162,7 +146,7 @@ def test_runs_clean_under_the_sanitizers(tmp_path, golden):
         got, want = run_lines(exe, tmp_path, text), oracle_rows(text)
         assert got == want
     src, dst = tmp_path / "q.txt", tmp_path / "q.out"
-    src.write_bytes(b"".join(t.encode() + b"\n" for t in _qual_texts()[:3000] + ["", ".", "1e", "1e400", ".5"]))
+    src.write_bytes(b"".join(t.encode() + b"\n" for t in F.qual_texts()[:3000] + ["", ".", "1e", "1e400", ".5"]))
     subprocess.run([exe, "quals", str(src), str(dst)], check=True)
     out = subprocess.run([exe, "bench", str(tmp_path / "in.vcf"), "4", "1"], check=True, capture_output=True).stdout
     assert out.startswith(b"{") and out.rstrip().endswith(b"}")

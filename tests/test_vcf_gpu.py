@@ -4,6 +4,7 @@ of every variant, the three export modes, the thread / wave threshold and the ba
 TAB search, every error class, interval traversal, QUAL texts the host converts."""
 import gzip
 import os
+import re
 import struct
 
 import numpy as np
@@ -11,11 +12,16 @@ import pytest
 
 from disq_amd import _lib
 from oracle import oracle as O
+import floatcases as F
 import textutil as T
 import vcfcases as K
 import vcfutil as V
+from floatref import BINARY64, exact_bits
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VCF_LONG = int(re.search(r"VCF_LONG = (\d+);", open(os.path.join(ROOT, "disq_amd", "csrc", "dq_vcf.hip")).read()).group(1))
 
 COLS = ("contig", "pos", "end", "flags", "n_alt", "n_filter", "n_info", "n_sample_cols")
 SAME_AS_TEXT = ("line_offset", "line_len", "hash", "part_offset", "part_digest")
@@ -285,7 +291,75 @@ def test_qual_texts_the_host_converts():
     assert b["qual"][4] == 12.5
 
 
-# ---- 6. edges
+# ---- 6. QUAL texts at the CPU test's scale: the device's f64 multiply / divide, the host's list
+def assert_quals_exact(want, texts):
+    """The oracle's float() pinned to the exact reference: variant i's QUAL is texts[i]'s binary64."""
+    assert len(want) == len(texts)
+    for f, t in zip(want, texts):
+        assert struct.unpack("<Q", struct.pack("<d", f["qual"]))[0] == exact_bits(t, BINARY64), t
+
+
+def test_qual_texts_bit_for_bit():
+    texts = [t.encode() for t in F.qual_texts()[:21000] + F.qual_edge_texts() + F.QUAL_EXTRA]
+    assert len(texts) == 21000 + 1200 + len(F.QUAL_EXTRA)
+    lines = [K.line(pos=b"%d" % (i + 1), qual=t) for i, t in enumerate(texts)]
+    data = T.bgzf_text(K.HEADER + b"".join(l + b"\n" for l in lines))
+    for split in (0, 70000):
+        b, want = assert_vcf_parity(data, split)
+        assert (len(b["part_offset"]) - 1 > 2) == bool(split)
+        host = sum(f["qual_host"] for f in want)
+        assert len(want) - host > len(lines) // 2            # the device's own path is what is under test
+        assert host > 1000 and b["n_qual_host"] == host
+    assert_quals_exact(want, texts)
+    # the edge of the exact path: 15 digits times 10^+-22 on the device, times 10^+-23 on the host
+    assert [f["qual_host"] for f in want[21000:22200]] == [i // 200 >= 4 for i in range(1200)]
+
+
+def _long_line_file():
+    """(text, QUAL texts, which lines are long): chr1 lines at POS 1000, 1010, ...; every other one
+    carries 600 genotype columns, which takes it past VCF_LONG; QUAL texts the device decides and
+    texts it leaves to the host in both kinds of line."""
+    edge = F.qual_edge_texts()
+    pool = edge[0:40] + edge[800:840] + edge[400:440] + edge[1000:1040] + F.QUAL_EXTRA
+    texts, lines, is_long = [], [], []
+    for i in range(320):
+        t = pool[(i // 2 + (len(pool) // 2) * (i % 2)) % len(pool)].encode()    # both kinds see the whole pool
+        rest = K.GT + (b"\t0|1:35:4" * 598 if i % 2 else b"")
+        texts.append(t)
+        lines.append(K.line(pos=b"%d" % (1000 + 10 * i), qual=t, rest=rest))
+        is_long.append(bool(i % 2))
+    assert all((len(l) > VCF_LONG) == k for l, k in zip(lines, is_long))
+    for k in (False, True):
+        fast = [V.qual_fast_path(t) for t, kk in zip(texts, is_long) if kk == k]
+        assert sum(fast) > 40 and len(fast) - sum(fast) > 40
+    return K.HEADER + b"".join(l + b"\n" for l in lines), texts, is_long
+
+
+def test_qual_in_long_lines():
+    text, texts, is_long = _long_line_file()
+    data = T.bgzf_text(text, block_u=8000)
+    for split in (0, 4000):
+        b, want = assert_vcf_parity(data, split)                 # all three export modes
+        assert b["n_qual_host"] == sum(not V.qual_fast_path(t) for t in texts) > 80
+        assert (len(b["part_offset"]) - 1 > 2) == bool(split)
+        assert int(b["n_sample_cols"].max()) == 600 and (b["line_len"] > VCF_LONG).tolist() == is_long
+    assert_quals_exact(want, texts)
+    # intervals: every line is validated (and its undecided QUAL counted), the kept ones are decoded
+    tbi = T.whole_file_tabix(["chr1", "chr2", "chrM"], len(data))
+    ivs = [("chr1", 1200, 1495), ("chr1", 2000, 2001), ("chr1", 3005, 3990), ("chr2", 1, 5000)]
+    keep = [any(lo <= 1000 + 10 * i <= hi for c, lo, hi in ivs if c == "chr1") for i in range(len(texts))]
+    all_host = sum(not V.qual_fast_path(t) for t in texts)
+    for split in (0, 4000):
+        b, want = assert_vcf_parity(data, split, ivs, tbi)
+        assert b["pos"].tolist() == [1000 + 10 * i for i, k in enumerate(keep) if k]
+        host = sum(not V.qual_fast_path(t) for t, k in zip(texts, keep) if k)
+        assert 0 < host < all_host and b["n_qual_host"] == host
+        kept_long = [l for l, k in zip(is_long, keep) if k]
+        assert (b["line_len"] > VCF_LONG).tolist() == kept_long and 20 < sum(kept_long) < len(kept_long)
+    assert_quals_exact(want, [t for t, k in zip(texts, keep) if k])
+
+
+# ---- 7. edges
 def test_header_only_file():
     text = b"".join(b"##meta=%d\n" % i for i in range(2000)) + K.HEADER
     data = T.bgzf_text(text, block_u=3000)
