@@ -100,6 +100,20 @@ class DqVariantBatch(C.Structure):
                 ("n_qual_host", C.c_int64)]
 
 
+class DqGenotypeBatch(C.Structure):
+    _fields_ = [("n_variants", C.c_int64), ("n_samples", C.c_int32), ("max_ploidy", C.c_int32),
+                ("flags", C.POINTER(C.c_uint8)), ("ploidy", C.POINTER(C.c_uint8)),
+                ("allele", C.POINTER(C.c_int16)), ("gq", C.POINTER(C.c_int32)),
+                ("dp", C.POINTER(C.c_int32)), ("cell_off", C.POINTER(C.c_int32)),
+                ("sample_name_off", C.POINTER(C.c_int32)),
+                ("sample_names", C.POINTER(C.c_uint8)),
+                ("n_partitions", C.c_int64), ("part_offset", C.POINTER(C.c_int64)),
+                ("n_gq_host", C.c_int64)]
+
+
+# dq_genotype_batch.flags (include/disq_gpu.h)
+GT_HAS_GT, GT_PHASED, GT_HAS_GQ, GT_HAS_DP, GT_FILTERED = 1, 2, 4, 8, 16
+
 # dq_vcf_read's export modes and dq_variant_batch.flags (include/disq_gpu.h)
 VCF_EXPORT_FIELDS, VCF_EXPORT_SITES, VCF_EXPORT_LINES = 0, 1, 2
 (VCF_HAS_ID, VCF_HAS_QUAL, VCF_UNFILTERED, VCF_PASS, VCF_INFO_END, VCF_HAS_GENOTYPES, VCF_SYMBOLIC,
@@ -149,7 +163,8 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_set_export_arena", "dq_checked_report", "dq_abi_version", "dq_write_bai",
            "dq_text_write_tbi", "dq_sam_open_memory", "dq_sam_open_path", "dq_sam_run",
            "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch",
-           "dq_vcf_run", "dq_vcf_read", "dq_variant_batch_free")
+           "dq_vcf_run", "dq_vcf_read", "dq_variant_batch_free", "dq_vcf_genotypes_run",
+           "dq_vcf_genotypes", "dq_genotype_batch_free")
 
 _lib = None
 _lock = threading.Lock()
@@ -223,6 +238,9 @@ def lib():
         L.dq_vcf_run.argtypes = [vp, P(DqStats)]
         L.dq_vcf_read.argtypes = [vp, C.c_int32, P(P(DqVariantBatch))]
         L.dq_variant_batch_free.argtypes = [P(DqVariantBatch)]
+        L.dq_vcf_genotypes_run.argtypes = [vp, P(DqStats)]
+        L.dq_vcf_genotypes.argtypes = [vp, P(P(DqGenotypeBatch))]
+        L.dq_genotype_batch_free.argtypes = [P(DqGenotypeBatch)]
         L.dq_sam_open_memory.argtypes = [vp, vp, C.c_int64]
         L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
         L.dq_sam_run.argtypes = [vp, P(DqStats)]
@@ -602,6 +620,43 @@ class Context:
             return out
         finally:
             lib().dq_variant_batch_free(bp)
+
+    # ---- VCF genotype decode (dq_vcf_genotypes*) of an open text context
+    def vcf_genotypes_run(self):
+        """The site decode when the context has not run it, then the genotype check and decode
+        passes; the matrix stays in HBM (dq_vcf_genotypes_run).  ms_records is the device time of
+        the site passes plus the genotype passes."""
+        st = DqStats()
+        check(self._h, lib().dq_vcf_genotypes_run(self._h, C.byref(st)))
+        return st
+
+    def vcf_genotypes(self):
+        """The genotype matrix of vcf_read's variants (dq_vcf_genotypes): dict of numpy arrays --
+        flags, ploidy, gq, dp and cell_off shaped (n, S), allele shaped (n, S, P), part_offset --
+        plus samples (the names, bytes), n_samples, max_ploidy and n_gq_host."""
+        bp = C.POINTER(DqGenotypeBatch)()
+        check(self._h, lib().dq_vcf_genotypes(self._h, C.byref(bp)))
+        try:
+            b = bp.contents
+            n, S, P = b.n_variants, b.n_samples, b.max_ploidy
+
+            def arr(ptr, k, dt):
+                if not k or not ptr:
+                    return np.zeros(0, dt)
+                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
+            no = arr(b.sample_name_off, S + 1, np.int32)
+            names = arr(b.sample_names, int(no[-1]) if len(no) else 0, np.uint8).tobytes()
+            return {"flags": arr(b.flags, n * S, np.uint8).reshape(n, S),
+                    "ploidy": arr(b.ploidy, n * S, np.uint8).reshape(n, S),
+                    "allele": arr(b.allele, n * S * P, np.int16).reshape(n, S, P),
+                    "gq": arr(b.gq, n * S, np.int32).reshape(n, S),
+                    "dp": arr(b.dp, n * S, np.int32).reshape(n, S),
+                    "cell_off": arr(b.cell_off, n * S, np.int32).reshape(n, S),
+                    "part_offset": arr(b.part_offset, b.n_partitions + 1, np.int64),
+                    "samples": [names[no[i]:no[i + 1]] for i in range(S)],
+                    "n_samples": int(S), "max_ploidy": int(P), "n_gq_host": int(b.n_gq_host)}
+        finally:
+            lib().dq_genotype_batch_free(bp)
 
     def text_write_tbi(self) -> bytes:
         """htsjdk TabixIndexCreator over the open text file (dq_text_write_tbi): the decompressed

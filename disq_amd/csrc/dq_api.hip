@@ -28,6 +28,7 @@
 #include "dq_internal.h"
 #include "dq_sam_core.h"
 #include "dq_vcf_core.h"
+#include "dq_vcf_gt_core.h"
 
 using namespace dq;
 
@@ -120,7 +121,7 @@ struct Bai {
 struct dq_ctx {
   dq_opts o{};
   hipStream_t s = nullptr;
-  hipEvent_t ev[12] = {};  // 8..11: the VCF validate and decode passes
+  hipEvent_t ev[16] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes
   // DQ_EXPORT_STREAMS=2: the export's device-to-pinned copies alternate between s and this second
   // stream (a second DMA engine); created on first use
   hipStream_t sx = nullptr;
@@ -164,6 +165,14 @@ struct dq_ctx {
   dq::VcfContigs vcf_ctg{};
   int64_t vcf_nqual_host = 0;
   double vcf_ms = 0;
+  // VCF genotype decode (dq_vcf_genotypes*) behind the site decode: the #CHROM line's sample names,
+  // the matrix of the kept variants at ploidy gt_P, the GQ texts the host converted
+  std::vector<std::string> vcf_samples;  // empty without vcf_G
+  int64_t gt_gen = -1;                   // the text run the matrix belongs to
+  int32_t gt_P = 0;
+  int64_t gt_nhost = 0;
+  double gt_ms = 0;
+  DevBuf g_scal, g_fix, g_flags, g_ploidy, g_allele, g_gq, g_dp, g_off;
   // SAM text path (dq_sam_*): C holds the text itself; the records are encoded into sam_rec (their
   // offsets in rec_lin, rows in the f_* arrays), the built BAM header is hdr.  The line scan shares
   // the text path's terminator and keep / scan buffers (a context is in one mode at a time).
@@ -2347,6 +2356,7 @@ static void reset_open(dq_ctx* ctx, int64_t len) {
   ctx->have_sam = false;
   ctx->vcf_hdr = false;
   ctx->vcf_gen = -1;
+  ctx->gt_gen = -1;
 }
 
 // Bytes [off, off + len) of an open file into C (plus the 4 KiB zero pad): read() into two pinned
@@ -3936,13 +3946,17 @@ static int vcf_header(dq_ctx* ctx) {
   dqv::VcfHeader H;
   std::vector<uint8_t> pre;
   const int64_t ulen = ctx->ulen;
+  int64_t pre_n = 0;
   for (int64_t n = std::min<int64_t>(ulen, 1 << 20);; n = std::min<int64_t>(ulen, n * 8)) {
+    pre_n = n;
     pre.resize((size_t)std::max<int64_t>(1, n));
     if (n > 0) HIPCHK(hipMemcpy(pre.data(), ctx->U.p, (size_t)n, hipMemcpyDeviceToHost));
     if (dqv::vcf_header_parse(pre.data(), n, n >= ulen, &H) == 0) break;
     if (n >= ulen) break;
   }
   if (H.has_data && !H.has_chrom) RET(DQ_EFORMAT, "VCF header: no #CHROM line");
+  ctx->vcf_samples.clear();
+  if (H.G) dqg::gt_header_samples(pre.data(), pre_n, &ctx->vcf_samples);
   dqv::ContigTableHost R;
   dqv::vcf_contig_table_build(H.contigs, &R);
   // one buffer: hashes | name offsets | indices | name bytes
@@ -4182,6 +4196,179 @@ void dq_variant_batch_free(dq_variant_batch* b) {
   free(b->part_digest);
   free(b->contig_name_off);
   free(b->contig_names);
+  free(b);
+}
+
+// ---- VCF genotype decode (row f10): AbstractVCFCodec.createGenotypeMap over the variants of the
+// site decode.  The check and decode passes of dq_vcf_gt.hip run on the
+// columns vcf_run left in HBM; the matrix stays there.
+static int gt_ensure(dq_ctx* ctx, DevBuf& b, size_t bytes) {
+  const hipError_t e = b.ensure(bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    RET(DQ_ENOMEM, "the genotype matrix does not fit in device memory");
+  }
+  HIPCHK(e);
+  return 0;
+}
+
+static int gt_run(dq_ctx* ctx) {
+  int rc = vcf_run(ctx);
+  if (rc) return rc;
+  if (ctx->gt_gen == ctx->text_gen) return 0;
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept, S = (int64_t)ctx->vcf_samples.size();
+  ctx->gt_P = S > 0 ? 1 : 0;
+  ctx->gt_nhost = 0;
+  ctx->gt_ms = 0;
+  if (S > 0 && n > 0) {
+    if (S > INT32_MAX || n > (INT64_MAX >> 12) / S) RET(DQ_ENOMEM, "the genotype matrix does not fit in device memory");
+    const int64_t cells = n * S;
+    const dq::GtIn in{ctx->U.as<uint8_t>(),       ctx->ulen,          ctx->t_vs.as<int64_t>(),
+                      ctx->t_vl.as<int32_t>(),    ctx->t_idx.as<int64_t>(), ctx->t_total,
+                      ctx->t_kept.as<int64_t>(),  n,                  ctx->v_colend.as<int32_t>(),
+                      ctx->v_nalt.as<int32_t>(),  ctx->v_nsample.as<int32_t>(), (int32_t)S};
+    // ---- check: first offender | largest ploidy | GQ texts for the host (| the decode pass's list)
+    if ((rc = ensure_all(ctx, ctx->g_scal, 64))) return rc;
+    unsigned long long* d_scal = ctx->g_scal.as<unsigned long long>();
+    const unsigned long long init[4] = {~0ull, 0, 0, 0};
+    unsigned long long sc[3] = {~0ull, 0, 0};
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(d_scal, init, sizeof init, hipMemcpyHostToDevice));
+    HIPCHK(hipEventRecord(ctx->ev[12], s));
+    dq::launch_gt_check(in, d_scal, s);
+    HIPCHK(hipEventRecord(ctx->ev[13], s));
+    HIPCHK(hipMemcpyAsync(sc, d_scal, sizeof sc, hipMemcpyDeviceToHost, s));  // one download: all three
+    HIPCHK(hipStreamSynchronize(s));
+    if (sc[0] != ~0ull) {
+      const int32_t st = (int32_t)(sc[0] & 0xff);
+      std::string msg = "VCF line " + std::to_string((long long)(sc[0] >> 32)) + ": ";
+      if (st >= dqg::GT_E_CELL) msg += "sample " + std::to_string((long long)((sc[0] >> 8) & 0xffffff)) + ": ";
+      RET(DQ_EFORMAT, msg + dqg::gt_status_name(st));
+    }
+    const int32_t P = (int32_t)std::max<unsigned long long>(1, std::min<unsigned long long>(sc[1], dqg::GT_MAX_PLOIDY));
+    const int64_t nhost = (int64_t)sc[2];
+    // ---- decode
+    if ((rc = gt_ensure(ctx, ctx->g_flags, (size_t)cells)) || (rc = gt_ensure(ctx, ctx->g_ploidy, (size_t)cells)) ||
+        (rc = gt_ensure(ctx, ctx->g_allele, 2 * (size_t)cells * (size_t)P)) ||
+        (rc = gt_ensure(ctx, ctx->g_gq, 4 * (size_t)cells)) || (rc = gt_ensure(ctx, ctx->g_dp, 4 * (size_t)cells)) ||
+        (rc = gt_ensure(ctx, ctx->g_off, 4 * (size_t)cells)) ||
+        (rc = gt_ensure(ctx, ctx->g_fix, 24 * (size_t)std::max<int64_t>(1, nhost))))
+      return rc;
+    const dq::GtCols out{ctx->g_flags.as<uint8_t>(), ctx->g_ploidy.as<uint8_t>(), ctx->g_allele.as<int16_t>(),
+                         ctx->g_gq.as<int32_t>(),    ctx->g_dp.as<int32_t>(),     ctx->g_off.as<int32_t>()};
+    HIPCHK(hipEventRecord(ctx->ev[14], s));
+    dq::launch_gt_decode(in, out, P, ctx->g_fix.as<int64_t>(), nhost, d_scal, s);
+    HIPCHK(hipEventRecord(ctx->ev[15], s));
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, d_scal + 3, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((int64_t)cnt != nhost) RET(DQ_EDEVICE, "VCF genotype decode pass: its GQ texts for the host differ from the check pass's count");
+    // ---- GQ fix-ups: the texts off the digit path, strtod and Java's rounding (normally none)
+    if (cnt > 0) {
+      std::vector<int64_t> ent(3 * (size_t)cnt);
+      HIPCHK(hipMemcpy(ent.data(), ctx->g_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
+      std::string txt;
+      for (size_t e = 0; e < (size_t)cnt; e++) {
+        const int64_t c = ent[3 * e], ta = ent[3 * e + 1], tn = ent[3 * e + 2];
+        if (c < 0 || c >= cells || ta < 0 || tn <= 0 || ta + tn > ctx->ulen)
+          RET(DQ_EDEVICE, "VCF genotype decode pass: bad fix-up entry");
+        txt.assign((size_t)tn, '\0');
+        HIPCHK(hipMemcpy(&txt[0], ctx->U.as<uint8_t>() + ta, (size_t)tn, hipMemcpyDeviceToHost));
+        const int32_t q = dqg::gt_round_gq(strtod(txt.c_str(), nullptr));
+        HIPCHK(hipMemcpy(ctx->g_gq.as<int32_t>() + c, &q, 4, hipMemcpyHostToDevice));
+      }
+    }
+    ctx->gt_P = P;
+    ctx->gt_nhost = nhost;
+    ctx->gt_ms = (double)ev_ms(ctx->ev[12], ctx->ev[13]) + (double)ev_ms(ctx->ev[14], ctx->ev[15]);
+  }
+  ctx->gt_gen = ctx->text_gen;
+  return 0;
+}
+
+int dq_vcf_genotypes_run(dq_ctx* ctx, dq_stats* stats) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  int rc = gt_run(ctx);
+  if (rc) return rc;
+  if (stats) {
+    *stats = ctx->stats;
+    stats->ms_plan += stats->ms_records;               // as dq_vcf_run
+    stats->ms_records = ctx->vcf_ms + ctx->gt_ms;      // validate + decode, genotype check + decode
+    stats->ms_total += ctx->vcf_ms + ctx->gt_ms;
+  }
+  return 0;
+}
+
+int dq_vcf_genotypes(dq_ctx* ctx, dq_genotype_batch** out) {
+  if (!ctx || !out) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  int rc = gt_run(ctx);
+  if (rc) return rc;
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
+  const size_t S = ctx->vcf_samples.size(), P = (size_t)ctx->gt_P;
+  const size_t cells = (size_t)n * S, c1 = std::max<size_t>(1, cells);
+  size_t name_bytes = 0;
+  for (const std::string& c : ctx->vcf_samples) name_bytes += c.size();
+  dq_genotype_batch* b = (dq_genotype_batch*)calloc(1, sizeof(dq_genotype_batch));
+  if (!b) return DQ_ENOMEM;
+  b->n_variants = n;
+  b->n_samples = (int32_t)S;
+  b->max_ploidy = (int32_t)P;
+  b->flags = (uint8_t*)malloc(c1);
+  b->ploidy = (uint8_t*)malloc(c1);
+  b->allele = (int16_t*)malloc(2 * std::max<size_t>(1, cells * P));
+  b->gq = (int32_t*)malloc(4 * c1);
+  b->dp = (int32_t*)malloc(4 * c1);
+  b->cell_off = (int32_t*)malloc(4 * c1);
+  b->sample_name_off = (int32_t*)malloc(4 * (S + 1));
+  b->sample_names = (uint8_t*)malloc(std::max<size_t>(1, name_bytes));
+  b->n_partitions = nsplit;
+  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
+  if (!(b->flags && b->ploidy && b->allele && b->gq && b->dp && b->cell_off && b->sample_name_off &&
+        b->sample_names && b->part_offset)) {
+    dq_genotype_batch_free(b);
+    return DQ_ENOMEM;
+  }
+  if (cells > 0) {
+    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
+        {b->flags, ctx->g_flags.p, cells},         {b->ploidy, ctx->g_ploidy.p, cells},
+        {b->allele, ctx->g_allele.p, 2 * cells * P}, {b->gq, ctx->g_gq.p, 4 * cells},
+        {b->dp, ctx->g_dp.p, 4 * cells},           {b->cell_off, ctx->g_off.p, 4 * cells}};
+    bool ok = true;
+    for (const auto& c : cp) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
+      dq_genotype_batch_free(b);
+      RET(DQ_EDEVICE, "dq_vcf_genotypes: device to host copy failed");
+    }
+  }
+  b->sample_name_off[0] = 0;
+  for (size_t r = 0; r < S; r++) {
+    const std::string& c = ctx->vcf_samples[r];
+    memcpy(b->sample_names + b->sample_name_off[r], c.data(), c.size());
+    b->sample_name_off[r + 1] = b->sample_name_off[r] + (int32_t)c.size();
+  }
+  for (int64_t i = 0; i < nsplit; i++) b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
+  b->part_offset[nsplit] = n;
+  b->n_gq_host = ctx->gt_nhost;
+  *out = b;
+  return 0;
+}
+
+void dq_genotype_batch_free(dq_genotype_batch* b) {
+  if (!b) return;
+  free(b->flags);
+  free(b->ploidy);
+  free(b->allele);
+  free(b->gq);
+  free(b->dp);
+  free(b->cell_off);
+  free(b->sample_name_off);
+  free(b->sample_names);
+  free(b->part_offset);
   free(b);
 }
 
@@ -4547,8 +4734,9 @@ int dq_checked_report(uint64_t words[4]) {
       words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
     }
   }
-  for (int u = 0; u < 2; u++) {  // and so do the SAM writer's unit and the VCF decode's
-    const uint64_t a = words[2], b = u ? dq::dq_chk_take_vcf() : dq::dq_chk_take_samw();
+  for (int u = 0; u < 3; u++) {  // and so do the SAM writer's unit and the VCF decodes' two
+    const uint64_t a = words[2],
+                   b = u == 0 ? dq::dq_chk_take_samw() : u == 1 ? dq::dq_chk_take_vcf() : dq::dq_chk_take_vcfgt();
     if (a == ~0ull || b == ~0ull) {
       words[2] = ~0ull;
     } else {

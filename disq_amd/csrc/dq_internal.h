@@ -47,8 +47,8 @@ enum : int {
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
   CHK_SAM = 15,      // SAM read and write (dq_sam.hip, dq_samw.hip share the bit): a line, size,
                      //     record-byte, line-byte or fix-up slot
-  CHK_VCF = 15,      // VCF site decode (dq_vcf.hip shares the bit): a line, column row, fix-up slot or
-                     //     site byte
+  CHK_VCF = 15,      // VCF site and genotype decode (dq_vcf.hip, dq_vcf_gt.hip share the bit): a line,
+                     //     column row, matrix cell, LDS offset slot, fix-up slot or site byte
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -463,6 +463,37 @@ void launch_vcf_decode(const uint8_t* U, int64_t ulen, const int64_t* vstart, co
 void launch_vcf_gather(const uint8_t* U, int64_t ulen, const int64_t* start, const int32_t* len,
                        const int64_t* out_off, int64_t n, uint8_t* out, hipStream_t s);
 
+// ------------------------------------------------------------------ VCF genotype decode (dq_vcf_gt.hip)
+struct GtIn {              // the kept variants of a text run, and what the site decode knows of them
+  const uint8_t* U;
+  int64_t ulen;
+  const int64_t* vstart;   // value start / length of the `total` lines of the list
+  const int32_t* vlen;
+  const int64_t* lidx;     // their indices in the file's line table
+  int64_t total;
+  const int64_t* kept;     // variant j = entry kept[j] of the list
+  int64_t n;
+  const int32_t* col_end;  // VcfCols of the same variants: FORMAT starts at col_end[8 j + 7] + 1
+  const int32_t* n_alt;
+  const int32_t* n_sample_cols;
+  int32_t S;               // the header's sample count, > 0
+};
+struct GtCols {            // the arrays of dq_genotype_batch, n * S cells, row-major by variant
+  uint8_t* flags;
+  uint8_t* ploidy;
+  int16_t* allele;         // P per cell
+  int32_t* gq;
+  int32_t* dp;
+  int32_t* cell_off;
+};
+// Check pass: scal[0] (all ones) takes the smallest dqg::gt_error_key, scal[1] (zero) the largest
+// ploidy, scal[2] (zero) the count of GQ texts left to the host; scal[3] is the decode pass's.
+void launch_gt_check(GtIn in, unsigned long long* scal, hipStream_t s);
+// Decode pass: the matrix at ploidy P; the host's GQ texts appended to fix (3 words each: cell,
+// text offset in U, text length), counted in scal[3] (zero).
+void launch_gt_decode(GtIn in, GtCols out, int32_t P, int64_t* fix, int64_t fix_cap,
+                      unsigned long long* scal, hipStream_t s);
+
 // ------------------------------------------------------------------ SAM writer (dq_samw.hip)
 struct SamwRefs {           // the header's reference names by index, see dq_samw_core.h
   const int32_t* name_off;  // n + 1 offsets into names
@@ -486,6 +517,7 @@ void launch_samw_format(const uint8_t* raw, int64_t raw_len, const int64_t* off,
 uint64_t dq_chk_take_sam();
 uint64_t dq_chk_take_samw();
 uint64_t dq_chk_take_vcf();
+uint64_t dq_chk_take_vcfgt();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

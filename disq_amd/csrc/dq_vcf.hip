@@ -21,6 +21,7 @@
 #define DQV_CHECK(cond) ((void)0)
 #endif
 #include "dq_vcf_core.h"
+#include "dq_vcf_stage.h"
 
 namespace dq {
 namespace {
@@ -76,38 +77,7 @@ __device__ inline bool data_line(const uint8_t* __restrict__ U, int64_t ulen, in
   return !(len > 0 && U[a] == '#');
 }
 
-// ---- the lines of up to VCF_LONG bytes, a thread per line
-// One thread reading its own line loads from 64 cache lines per wave instruction, so a block first
-// copies the span of the stream its 256 lines cover into LDS with 16-byte loads (consecutive lanes,
-// consecutive words; the lines of the list are ascending in U, so the span runs from the first
-// line's start to the last line's end) and the threads walk from there.  A block whose span does
-// not fit (long lines among its lines, or kept lines far apart under an interval filter) walks
-// from memory; so does a thread whose line lies outside the block's span.  The copy reads whole
-// 16-byte words of [lo & ~15, hi): inside the stream, or in the zero bytes behind it.
-constexpr int32_t VCF_STAGE = 40960;  // LDS bytes per block: 160 bytes a line
-
-struct StageSpan {
-  int64_t lo, hi;  // stage holds the stream's bytes [lo, hi); lo is 16-byte aligned
-  bool staged;
-};
-
-__device__ inline StageSpan stage_span(const uint8_t* __restrict__ U, int64_t ulen, int64_t first,
-                                       int64_t last_end, uint8_t* __restrict__ stage) {
-  StageSpan sp;
-  sp.lo = first & ~(int64_t)15;
-  const int64_t nb = (last_end - sp.lo + 15) & ~(int64_t)15;
-  sp.staged = first >= 0 && last_end >= first && last_end <= ulen && nb <= VCF_STAGE;  // block-uniform
-  sp.hi = sp.staged ? sp.lo + nb : sp.lo;
-  if (sp.staged) {
-    for (int64_t i = (int64_t)threadIdx.x * 16; i < nb; i += 256 * 16) {
-      DQ_CHK(sp.lo + i + 16 <= ulen + 256 && i + 16 <= VCF_STAGE, CHK_VCF);  // U's zero pad: 256 bytes
-      *reinterpret_cast<uint4*>(stage + i) = *reinterpret_cast<const uint4*>(U + sp.lo + i);
-    }
-  }
-  __syncthreads();
-  return sp;
-}
-
+// ---- the lines of up to VCF_LONG bytes, a thread per line (their staging: dq_vcf_stage.h)
 __global__ __launch_bounds__(256) void vcf_validate_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ vstart,
     const int32_t* __restrict__ vlen, const int64_t* __restrict__ lidx, int64_t n, int32_t G,

@@ -401,6 +401,20 @@ def variant_sites(b):
     return [VariantsPartition(rows[po[p]:po[p + 1]]) for p in range(len(po) - 1)]
 
 
+class GenotypesPartition:
+    """One partition's rows of the genotype matrix (Context.vcf_genotypes): flags, ploidy, gq, dp and
+    cell_off shaped (rows, S), allele shaped (rows, S, P); row k belongs to the partition's variant
+    k."""
+    __slots__ = ("flags", "ploidy", "allele", "gq", "dp", "cell_off")
+
+    def __init__(self, g, lo, hi):
+        for k in self.__slots__:
+            setattr(self, k, g[k][lo:hi])
+
+    def __len__(self):
+        return len(self.flags)
+
+
 class VariantsRDD:
     def __init__(self, partitions):
         self.partitions = partitions
@@ -416,9 +430,22 @@ class VariantsRDD:
 
 
 class HtsjdkVariantsRdd:
-    def __init__(self, header_lines, variants: VariantsRDD):
+    def __init__(self, header_lines, variants: VariantsRDD, genotypes=None):
         self._header = header_lines
         self._variants = variants
+        self._genotypes = genotypes
+
+    def getSampleNames(self):
+        """The #CHROM line's sample names (read(genotypes=True)), else None."""
+        return None if self._genotypes is None else list(self._genotypes["samples"])
+
+    def getGenotypes(self):
+        """One GenotypesPartition per partition (read(genotypes=True)), else None."""
+        g = self._genotypes
+        if g is None:
+            return None
+        po = g["part_offset"]
+        return [GenotypesPartition(g, int(po[p]), int(po[p + 1])) for p in range(len(po) - 1)]
 
     def getHeader(self):
         """The '#' lines of the file (VCFHeader source text)."""
@@ -448,9 +475,13 @@ class HtsjdkVariantsRddStorage:
         return self
 
     def read(self, path: str, intervals: Optional[Sequence[Interval]] = None,
-             decode: bool = False) -> HtsjdkVariantsRdd:
+             decode: bool = False, genotypes: bool = False) -> HtsjdkVariantsRdd:
         """decode: each partition holds VariantSite rows (the device's VCFCodec.decode, SITES
-        export: only the first eight columns' bytes cross to the host) instead of line bytes."""
+        export: only the first eight columns' bytes cross to the host) instead of line bytes.
+        genotypes (with decode): the sample columns decoded on the device as well
+        (dq_vcf_genotypes); the rdd then answers getSampleNames() and getGenotypes()."""
+        if genotypes and not decode:
+            raise ValueError("genotypes=True needs decode=True")
         if not (path.endswith(".gz") or path.endswith(".bgz")):
             raise ValueError(f"{path}: the GPU text path reads BGZF-compressed VCF (.vcf.gz/.vcf.bgz)")
         with _lib.Context(split_size=self._split_size, device=self._device) as ctx:
@@ -464,8 +495,9 @@ class HtsjdkVariantsRddStorage:
                 ctx.text_set_intervals([(iv.getContig(), iv.getStart(), iv.getEnd())
                                         for iv in intervals])
             b = ctx.vcf_read(_lib.VCF_EXPORT_SITES) if decode else ctx.text_read(True)
+            g = ctx.vcf_genotypes() if genotypes else None
         if decode:
-            return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(variant_sites(b)))
+            return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(variant_sites(b)), g)
         d, do, ln, po = b["data"], b["data_offset"], b["line_len"], b["part_offset"]
         parts = [VariantsPartition(bytes(d[do[k]:do[k] + ln[k]]) for k in range(po[p], po[p + 1]))
                  for p in range(len(po) - 1)]

@@ -30,6 +30,8 @@
  *     (D/impl/formats/sam/SamSink.java:37)                                  dq_sam_write
  *   VCFCodec.decode of every data line, the step of VcfSource.getVariants between the '#'
  *     filter and the overlap filter (D/impl/formats/vcf/VcfSource.java:113)    dq_vcf_read
+ *   AbstractVCFCodec.createGenotypeMap, what VariantContext.getGenotypes() runs on the text
+ *     LazyGenotypesContext kept, over the variants VcfSource.getVariants hands out  dq_vcf_genotypes
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -453,6 +455,50 @@ typedef struct dq_variant_batch {
 int dq_vcf_run(dq_ctx* ctx, dq_stats* stats);
 int dq_vcf_read(dq_ctx* ctx, int32_t mode, dq_variant_batch** out);
 void dq_variant_batch_free(dq_variant_batch* b);
+
+/* ---- VCF genotype decode: createGenotypeMap -------------------
+ * The FORMAT column and the sample columns of the variants of dq_vcf_read on the same context --
+ * the same lines in the same order and partitions, after the same tabix pruning and overlap filter
+ * -- decoded on the device into a dense variants x samples matrix: what htsjdk's
+ * AbstractVCFCodec.createGenotypeMap / parseGenotypeAlleles compute when a consumer asks a
+ * VariantContext for its genotypes.  The rules are DESIGN.md section 16.  S, the sample count, is 0
+ * for a header without a sample (not an error: empty arrays), else the number of columns of the
+ * #CHROM line behind the ninth with trailing empty ones dropped.  GT, GQ, DP and FT are read; the
+ * other keys' text is reached through cell_off.  Both calls run the site decode first when the
+ * context has not (its errors come first, unchanged); then only the variants handed out are
+ * checked, as htsjdk parses genotypes lazily: the first failing check gives DQ_EFORMAT and
+ * dq_last_error "VCF line <k>: samples", "VCF line <k>: FORMAT" or
+ * "VCF line <k>: sample <s>: <GT|GQ|DP|cell>", k as dq_vcf_read counts lines and the lowest
+ * offender, s the lowest offending 0-based sample of that line.  dq_vcf_read and the dq_text_*
+ * calls work on the same context afterwards.  A BAM or SAM context or no open file gives DQ_EINVAL,
+ * a matrix that does not fit DQ_ENOMEM. */
+#define DQ_GT_HAS_GT 1      /* the first FORMAT key is GT and the cell has a value for it */
+#define DQ_GT_PHASED 2
+#define DQ_GT_HAS_GQ 4
+#define DQ_GT_HAS_DP 8
+#define DQ_GT_FILTERED 16   /* an FT value that is neither "." nor "PASS" */
+typedef struct dq_genotype_batch {
+  int64_t n_variants;      /* = dq_vcf_read's, row k is its variant k */
+  int32_t n_samples;       /* S */
+  int32_t max_ploidy;      /* P: the largest ploidy of any cell, at least 1 when S > 0 */
+  uint8_t* flags;          /* [n_variants * S], row-major by variant */
+  uint8_t* ploidy;         /* [n_variants * S] */
+  int16_t* allele;         /* [n_variants * S * P]: allele index, -1 no-call, -2 past the cell's ploidy */
+  int32_t* gq;             /* [n_variants * S], -1 when missing */
+  int32_t* dp;             /* [n_variants * S], -1 when missing */
+  int32_t* cell_off;       /* [n_variants * S]: offset of the sample column's first byte in the line's
+                              value (it ends at the next one's offset - 1, the last at line_len) */
+  int32_t* sample_name_off; uint8_t* sample_names;   /* S + 1 offsets */
+  int64_t n_partitions; int64_t* part_offset;        /* as dq_vcf_read */
+  int64_t n_gq_host;       /* GQ texts off the device's digit path, converted by the host's strtod */
+} dq_genotype_batch;
+/* The site decode when the context has not run it, then the genotype check and decode passes; the
+ * matrix stays in HBM.  stats: dq_vcf_run's, with the device time of the two genotype passes added
+ * to ms_records (so ms_records = site validate + decode + genotype check + decode) and to
+ * ms_total. */
+int dq_vcf_genotypes_run(dq_ctx* ctx, dq_stats* stats);
+int dq_vcf_genotypes(dq_ctx* ctx, dq_genotype_batch** out);
+void dq_genotype_batch_free(dq_genotype_batch* b);
 
 /* ---- SAM text: SamSource.getReads -----------------------------
  * An uncompressed SAM file read as Disq reads it (D/impl/formats/sam/SamSource.java:36-77): Hadoop
