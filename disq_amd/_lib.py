@@ -111,6 +111,28 @@ class DqGenotypeBatch(C.Structure):
                 ("n_gq_host", C.c_int64)]
 
 
+class DqInfoKey(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("type", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DqInfoBatch(C.Structure):
+    _fields_ = [("n_variants", C.c_int64), ("n_keys", C.c_int32), ("reserved", C.c_int32),
+                ("key_type", C.POINTER(C.c_int32)), ("key_width", C.POINTER(C.c_int32)),
+                ("key_base", C.POINTER(C.c_int64)), ("flags", C.POINTER(C.c_uint8)),
+                ("n_values", C.POINTER(C.c_int32)), ("val_off", C.POINTER(C.c_int32)),
+                ("val_len", C.POINTER(C.c_int32)),
+                ("ival", C.POINTER(C.c_int32)), ("n_ival", C.c_int64),
+                ("fval", C.POINTER(C.c_double)), ("n_fval", C.c_int64),
+                ("n_partitions", C.c_int64), ("part_offset", C.POINTER(C.c_int64)),
+                ("n_float_host", C.c_int64)]
+
+
+# dq_info_key.type, dq_info_batch.flags and the missing values (include/disq_gpu.h)
+INFO_AUTO, INFO_FLAG, INFO_INTEGER, INFO_FLOAT, INFO_STRING = 0, 1, 2, 3, 4
+INFO_PRESENT, INFO_HAS_VALUE, INFO_REPEATED = 1, 2, 4
+INFO_I_MISSING = -2 ** 31
+INFO_F_MISSING_BITS = 0x7ff8000000000001
+
 # dq_genotype_batch.flags (include/disq_gpu.h)
 GT_HAS_GT, GT_PHASED, GT_HAS_GQ, GT_HAS_DP, GT_FILTERED = 1, 2, 4, 8, 16
 
@@ -164,7 +186,8 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_text_write_tbi", "dq_sam_open_memory", "dq_sam_open_path", "dq_sam_run",
            "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch",
            "dq_vcf_run", "dq_vcf_read", "dq_variant_batch_free", "dq_vcf_genotypes_run",
-           "dq_vcf_genotypes", "dq_genotype_batch_free")
+           "dq_vcf_genotypes", "dq_genotype_batch_free", "dq_vcf_info_run", "dq_vcf_info",
+           "dq_info_batch_free")
 
 _lib = None
 _lock = threading.Lock()
@@ -241,6 +264,9 @@ def lib():
         L.dq_vcf_genotypes_run.argtypes = [vp, P(DqStats)]
         L.dq_vcf_genotypes.argtypes = [vp, P(P(DqGenotypeBatch))]
         L.dq_genotype_batch_free.argtypes = [P(DqGenotypeBatch)]
+        L.dq_vcf_info_run.argtypes = [vp, P(DqInfoKey), C.c_int32, P(DqStats)]
+        L.dq_vcf_info.argtypes = [vp, P(DqInfoKey), C.c_int32, P(P(DqInfoBatch))]
+        L.dq_info_batch_free.argtypes = [P(DqInfoBatch)]
         L.dq_sam_open_memory.argtypes = [vp, vp, C.c_int64]
         L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
         L.dq_sam_run.argtypes = [vp, P(DqStats)]
@@ -657,6 +683,70 @@ class Context:
                     "n_samples": int(S), "max_ploidy": int(P), "n_gq_host": int(b.n_gq_host)}
         finally:
             lib().dq_genotype_batch_free(bp)
+
+    # ---- VCF INFO decode (dq_vcf_info*) of an open text context
+    @staticmethod
+    def _info_keys(keys):
+        """keys: ids (str or bytes) or (id, INFO_* type) pairs, as a dq_info_key array and the ids."""
+        ids, arr = [], (DqInfoKey * max(1, len(keys)))()
+        for q, k in enumerate(keys):
+            vid, ty = (k, INFO_AUTO) if isinstance(k, (str, bytes)) else k
+            vid = vid.encode() if isinstance(vid, str) else bytes(vid)
+            if b"\0" in vid:
+                raise ValueError("an INFO key holds a NUL byte")
+            ids.append(vid)
+            arr[q] = DqInfoKey(vid, int(ty), 0)
+        return arr, ids
+
+    def vcf_info_run(self, keys):
+        """The site decode when the context has not run it, then the INFO check and decode passes
+        for these keys; the columns stay in HBM (dq_vcf_info_run).  ms_records is the device time of
+        the site passes plus the INFO passes."""
+        arr, ids = self._info_keys(keys)
+        st = DqStats()
+        check(self._h, lib().dq_vcf_info_run(self._h, arr, len(ids), C.byref(st)))
+        return st
+
+    def vcf_info(self, keys):
+        """The INFO columns of vcf_read's variants for these keys (dq_vcf_info): dict of numpy
+        arrays -- flags, n_values, val_off and val_len shaped (K, n), key_type, key_width and
+        key_base shaped (K,), ival and fval flat, part_offset -- plus keys (the ids, bytes),
+        n_float_host and values: per key a view of its block of ival or fval shaped (n,) at width
+        1 and (n, W) above it, None for a FLAG or STRING key.  Missing elements are
+        INFO_I_MISSING and the NaN of INFO_F_MISSING_BITS (compare fval.view(np.uint64))."""
+        arr, ids = self._info_keys(keys)
+        bp = C.POINTER(DqInfoBatch)()
+        check(self._h, lib().dq_vcf_info(self._h, arr, len(ids), C.byref(bp)))
+        try:
+            b = bp.contents
+            n, K = b.n_variants, b.n_keys
+
+            def arr_of(ptr, k, dt):
+                if not k or not ptr:
+                    return np.zeros(0, dt)
+                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
+            g = {"flags": arr_of(b.flags, K * n, np.uint8).reshape(K, n),
+                 "n_values": arr_of(b.n_values, K * n, np.int32).reshape(K, n),
+                 "val_off": arr_of(b.val_off, K * n, np.int32).reshape(K, n),
+                 "val_len": arr_of(b.val_len, K * n, np.int32).reshape(K, n),
+                 "key_type": arr_of(b.key_type, K, np.int32), "key_width": arr_of(b.key_width, K, np.int32),
+                 "key_base": arr_of(b.key_base, K, np.int64),
+                 "ival": arr_of(b.ival, b.n_ival, np.int32), "fval": arr_of(b.fval, b.n_fval, np.float64),
+                 "part_offset": arr_of(b.part_offset, b.n_partitions + 1, np.int64),
+                 "keys": ids, "n_float_host": int(b.n_float_host)}
+            vals = []
+            for q in range(K):
+                ty, W, at = int(g["key_type"][q]), int(g["key_width"][q]), int(g["key_base"][q])
+                src = g["ival"] if ty == INFO_INTEGER else g["fval"] if ty == INFO_FLOAT else None
+                if src is None:
+                    vals.append(None)
+                else:
+                    v = src[at:at + n * W]
+                    vals.append(v if W == 1 else v.reshape(n, W))
+            g["values"] = vals
+            return g
+        finally:
+            lib().dq_info_batch_free(bp)
 
     def text_write_tbi(self) -> bytes:
         """htsjdk TabixIndexCreator over the open text file (dq_text_write_tbi): the decompressed

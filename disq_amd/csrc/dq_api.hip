@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -29,6 +30,7 @@
 #include "dq_sam_core.h"
 #include "dq_vcf_core.h"
 #include "dq_vcf_gt_core.h"
+#include "dq_vcf_info_core.h"
 
 using namespace dq;
 
@@ -121,7 +123,8 @@ struct Bai {
 struct dq_ctx {
   dq_opts o{};
   hipStream_t s = nullptr;
-  hipEvent_t ev[16] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes
+  hipEvent_t ev[20] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes;
+                           // 16..19: the INFO passes
   // DQ_EXPORT_STREAMS=2: the export's device-to-pinned copies alternate between s and this second
   // stream (a second DMA engine); created on first use
   hipStream_t sx = nullptr;
@@ -173,6 +176,16 @@ struct dq_ctx {
   int64_t gt_nhost = 0;
   double gt_ms = 0;
   DevBuf g_scal, g_fix, g_flags, g_ploidy, g_allele, g_gq, g_dp, g_off;
+  // VCF INFO decode (dq_vcf_info*) behind the site decode: the header's ##INFO types, the key list
+  // the resident columns belong to (info_sig: ids and types as given) and their shapes
+  std::map<std::string, int32_t> vcf_info_types;
+  int64_t info_gen = -1;  // the text run the columns belong to
+  std::string info_sig;
+  std::vector<int32_t> info_type, info_width;
+  std::vector<int64_t> info_base;
+  int64_t info_nival = 0, info_nfval = 0, info_nhost = 0;
+  double info_ms = 0;
+  DevBuf i_keys, i_scal, i_meta, i_fix, i_flags, i_nval, i_off, i_len, i_ival, i_fval;
   // SAM text path (dq_sam_*): C holds the text itself; the records are encoded into sam_rec (their
   // offsets in rec_lin, rows in the f_* arrays), the built BAM header is hdr.  The line scan shares
   // the text path's terminator and keep / scan buffers (a context is in one mode at a time).
@@ -2357,6 +2370,7 @@ static void reset_open(dq_ctx* ctx, int64_t len) {
   ctx->vcf_hdr = false;
   ctx->vcf_gen = -1;
   ctx->gt_gen = -1;
+  ctx->info_gen = -1;
 }
 
 // Bytes [off, off + len) of an open file into C (plus the 4 KiB zero pad): read() into two pinned
@@ -3957,6 +3971,7 @@ static int vcf_header(dq_ctx* ctx) {
   if (H.has_data && !H.has_chrom) RET(DQ_EFORMAT, "VCF header: no #CHROM line");
   ctx->vcf_samples.clear();
   if (H.G) dqg::gt_header_samples(pre.data(), pre_n, &ctx->vcf_samples);
+  dqi::info_header_types(pre.data(), pre_n, &ctx->vcf_info_types);
   dqv::ContigTableHost R;
   dqv::vcf_contig_table_build(H.contigs, &R);
   // one buffer: hashes | name offsets | indices | name bytes
@@ -4372,6 +4387,237 @@ void dq_genotype_batch_free(dq_genotype_batch* b) {
   free(b);
 }
 
+// ---- VCF INFO decode (row f11): AbstractVCFCodec.parseInfo over the variants of the site decode,
+// projected onto the caller's keys.  The check and decode passes of dq_vcf_info.hip (DESIGN.md
+// section 17) run on the col_end vcf_run left in HBM; the columns stay there.
+static int info_ensure(dq_ctx* ctx, DevBuf& b, size_t bytes) {
+  const hipError_t e = b.ensure(std::max<size_t>(8, bytes));
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    RET(DQ_ENOMEM, "the INFO columns do not fit in device memory");
+  }
+  HIPCHK(e);
+  return 0;
+}
+
+static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
+  if (ctx->sam_mode || !ctx->text_mode) RET(DQ_EINVAL, "not a text context (dq_text_open_*)");
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  if (!keys || n_keys < 1 || n_keys > dqi::INFO_MAX_KEYS) RET(DQ_EINVAL, "dq_vcf_info: 1 to 64 keys are taken");
+  std::vector<std::string> ids;
+  std::vector<int32_t> types;
+  std::string sig;
+  for (int32_t q = 0; q < n_keys; q++) {
+    if (!keys[q].id) RET(DQ_EINVAL, "dq_vcf_info: a key without an id");
+    ids.push_back(keys[q].id);
+    types.push_back(keys[q].type);
+    sig += ids.back() + "=" + std::to_string(keys[q].type) + ";";
+  }
+  dqi::InfoKeysHost KT;
+  if (const char* why = dqi::info_key_table_build(ids, types, {}, &KT)) RET(DQ_EINVAL, std::string("dq_vcf_info: ") + why);
+  int rc = vcf_run(ctx);
+  if (rc) return rc;
+  if (ctx->info_gen == ctx->text_gen && ctx->info_sig == sig) return 0;
+  ctx->info_gen = -1;
+  if (const char* why = dqi::info_key_table_build(ids, types, ctx->vcf_info_types, &KT))
+    RET(DQ_EINVAL, std::string("dq_vcf_info: ") + why);
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept, K = n_keys;
+  // one buffer: hashes | sorted indices | id offsets | types | header Flag marks | id bytes
+  const size_t o_hash = 0, o_idx = 8 * (size_t)K, o_off = o_idx + 4 * (size_t)K, o_type = o_off + 4 * (size_t)(K + 1),
+               o_hflag = o_type + (size_t)K, o_ids = o_hflag + (size_t)K;
+  std::vector<uint8_t> buf(o_ids + KT.ids.size() + 8);
+  memcpy(&buf[o_hash], KT.hash.data(), 8 * (size_t)K);
+  memcpy(&buf[o_idx], KT.idx.data(), 4 * (size_t)K);
+  memcpy(&buf[o_off], KT.id_off.data(), 4 * (size_t)(K + 1));
+  memcpy(&buf[o_type], KT.type.data(), (size_t)K);
+  memcpy(&buf[o_hflag], KT.hflag.data(), (size_t)K);
+  memcpy(&buf[o_ids], KT.ids.data(), KT.ids.size());
+  if ((rc = ensure_all(ctx, ctx->i_keys, buf.size())) || (rc = ensure_all(ctx, ctx->i_scal, 512)) ||
+      (rc = ensure_all(ctx, ctx->i_meta, 768)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(ctx->i_keys.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  const uint8_t* d = ctx->i_keys.as<uint8_t>();
+  const dq::InfoIn in{ctx->U.as<uint8_t>(),      ctx->ulen,
+                      ctx->t_vs.as<int64_t>(),   ctx->t_vl.as<int32_t>(),
+                      ctx->t_idx.as<int64_t>(),  ctx->t_total,
+                      ctx->t_kept.as<int64_t>(), n,
+                      ctx->v_colend.as<int32_t>(),
+                      dq::InfoKeysDev{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
+                                      (const int32_t*)(d + o_off), d + o_ids, d + o_type, d + o_hflag, (int32_t)K}};
+  // ---- check: first offender | Float texts for the host | the decode pass's list; widths behind
+  struct {
+    unsigned long long sc[8];
+    int32_t width[64];
+  } h;
+  h.sc[0] = ~0ull;
+  for (int i = 1; i < 8; i++) h.sc[i] = 0;
+  for (int i = 0; i < 64; i++) h.width[i] = 1;
+  unsigned long long* d_scal = ctx->i_scal.as<unsigned long long>();
+  int32_t* d_width = (int32_t*)(d_scal + 8);
+  HIPCHK(hipMemcpy(d_scal, &h, sizeof h, hipMemcpyHostToDevice));
+  HIPCHK(hipEventRecord(ctx->ev[16], s));
+  dq::launch_info_check(in, d_scal, d_width, s);
+  HIPCHK(hipEventRecord(ctx->ev[17], s));
+  HIPCHK(hipMemcpyAsync(&h, d_scal, sizeof h, hipMemcpyDeviceToHost, s));  // one download
+  HIPCHK(hipStreamSynchronize(s));
+  if (h.sc[0] != ~0ull) {
+    const size_t q = (size_t)(h.sc[0] & 0xff);
+    RET(DQ_EFORMAT, "VCF line " + std::to_string((long long)(h.sc[0] >> 8)) + ": INFO " + (q < ids.size() ? ids[q] : "?"));
+  }
+  const int64_t nhost = (int64_t)h.sc[1];
+  // ---- the columns' shapes
+  std::vector<int32_t> type((size_t)K), width((size_t)K);
+  std::vector<int64_t> base((size_t)K, -1);
+  int64_t nival = 0, nfval = 0;
+  for (int64_t q = 0; q < K; q++) {
+    type[(size_t)q] = KT.type[(size_t)q];
+    const int32_t W = std::max<int32_t>(1, h.width[q]);
+    width[(size_t)q] = W;
+    if (type[(size_t)q] != dqi::INFO_INTEGER && type[(size_t)q] != dqi::INFO_FLOAT) continue;
+    int64_t& tot = type[(size_t)q] == dqi::INFO_INTEGER ? nival : nfval;
+    if (n > 0 && (int64_t)W > (1ll << 40) / n) RET(DQ_ENOMEM, "the INFO columns do not fit in device memory");
+    base[(size_t)q] = tot;
+    tot += n * W;
+    if (tot > (1ll << 42)) RET(DQ_ENOMEM, "the INFO columns do not fit in device memory");
+  }
+  {
+    uint8_t meta[768];
+    memcpy(meta, base.data(), 8 * (size_t)K);
+    memcpy(meta + 512, width.data(), 4 * (size_t)K);
+    HIPCHK(hipMemcpy(ctx->i_meta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+  }
+  // ---- decode
+  const size_t cells = (size_t)K * (size_t)n;
+  if ((rc = info_ensure(ctx, ctx->i_flags, cells)) || (rc = info_ensure(ctx, ctx->i_nval, 4 * cells)) ||
+      (rc = info_ensure(ctx, ctx->i_off, 4 * cells)) || (rc = info_ensure(ctx, ctx->i_len, 4 * cells)) ||
+      (rc = info_ensure(ctx, ctx->i_ival, 4 * (size_t)nival)) || (rc = info_ensure(ctx, ctx->i_fval, 8 * (size_t)nfval)) ||
+      (rc = info_ensure(ctx, ctx->i_fix, 40 * (size_t)std::max<int64_t>(1, nhost))))
+    return rc;
+  const dq::InfoCols out{ctx->i_flags.as<uint8_t>(), ctx->i_nval.as<int32_t>(), ctx->i_off.as<int32_t>(),
+                         ctx->i_len.as<int32_t>(),   ctx->i_ival.as<int32_t>(), nival,
+                         ctx->i_fval.as<uint64_t>(), nfval,
+                         ctx->i_meta.as<int64_t>(),  (const int32_t*)(ctx->i_meta.as<uint8_t>() + 512)};
+  HIPCHK(hipEventRecord(ctx->ev[18], s));
+  dq::launch_info_decode(in, out, ctx->i_fix.as<int64_t>(), nhost, d_scal, s);
+  HIPCHK(hipEventRecord(ctx->ev[19], s));
+  unsigned long long cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if ((int64_t)cnt != nhost) RET(DQ_EDEVICE, "VCF INFO decode pass: its Float texts for the host differ from the check pass's count");
+  // ---- Float fix-ups: the texts off the exact path, converted by strtod (normally none)
+  if (cnt > 0) {
+    std::vector<int64_t> ent(5 * (size_t)cnt);
+    HIPCHK(hipMemcpy(ent.data(), ctx->i_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
+    std::string txt;
+    for (size_t e = 0; e < (size_t)cnt; e++) {
+      const int64_t q = ent[5 * e], k = ent[5 * e + 1], j = ent[5 * e + 2], ta = ent[5 * e + 3], tn = ent[5 * e + 4];
+      if (q < 0 || q >= K || type[(size_t)q] != dqi::INFO_FLOAT || k < 0 || k >= n || j < 0 || j >= width[(size_t)q] ||
+          ta < 0 || tn <= 0 || ta + tn > ctx->ulen)
+        RET(DQ_EDEVICE, "VCF INFO decode pass: bad fix-up entry");
+      txt.assign((size_t)tn, '\0');
+      HIPCHK(hipMemcpy(&txt[0], ctx->U.as<uint8_t>() + ta, (size_t)tn, hipMemcpyDeviceToHost));
+      const double v = strtod(txt.c_str(), nullptr);
+      HIPCHK(hipMemcpy(ctx->i_fval.as<double>() + base[(size_t)q] + k * width[(size_t)q] + j, &v, 8, hipMemcpyHostToDevice));
+    }
+  }
+  ctx->info_type = type;
+  ctx->info_width = width;
+  ctx->info_base = base;
+  ctx->info_nival = nival;
+  ctx->info_nfval = nfval;
+  ctx->info_nhost = nhost;
+  ctx->info_ms = n > 0 ? (double)ev_ms(ctx->ev[16], ctx->ev[17]) + (double)ev_ms(ctx->ev[18], ctx->ev[19]) : 0.0;
+  ctx->info_sig = sig;
+  ctx->info_gen = ctx->text_gen;
+  return 0;
+}
+
+int dq_vcf_info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_stats* stats) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  int rc = info_run(ctx, keys, n_keys);
+  if (rc) return rc;
+  if (stats) {
+    *stats = ctx->stats;
+    stats->ms_plan += stats->ms_records;             // as dq_vcf_run
+    stats->ms_records = ctx->vcf_ms + ctx->info_ms;  // validate + decode, INFO check + decode
+    stats->ms_total += ctx->vcf_ms + ctx->info_ms;
+  }
+  return 0;
+}
+
+int dq_vcf_info(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_info_batch** out) {
+  if (!ctx || !out) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  int rc = info_run(ctx, keys, n_keys);
+  if (rc) return rc;
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
+  const size_t K = (size_t)n_keys, cells = K * (size_t)n, c1 = std::max<size_t>(1, cells);
+  const size_t nival = (size_t)ctx->info_nival, nfval = (size_t)ctx->info_nfval;
+  dq_info_batch* b = (dq_info_batch*)calloc(1, sizeof(dq_info_batch));
+  if (!b) return DQ_ENOMEM;
+  b->n_variants = n;
+  b->n_keys = n_keys;
+  b->key_type = (int32_t*)malloc(4 * K);
+  b->key_width = (int32_t*)malloc(4 * K);
+  b->key_base = (int64_t*)malloc(8 * K);
+  b->flags = (uint8_t*)malloc(c1);
+  b->n_values = (int32_t*)malloc(4 * c1);
+  b->val_off = (int32_t*)malloc(4 * c1);
+  b->val_len = (int32_t*)malloc(4 * c1);
+  b->ival = (int32_t*)malloc(4 * std::max<size_t>(1, nival));
+  b->n_ival = (int64_t)nival;
+  b->fval = (double*)malloc(8 * std::max<size_t>(1, nfval));
+  b->n_fval = (int64_t)nfval;
+  b->n_partitions = nsplit;
+  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
+  if (!(b->key_type && b->key_width && b->key_base && b->flags && b->n_values && b->val_off && b->val_len &&
+        b->ival && b->fval && b->part_offset)) {
+    dq_info_batch_free(b);
+    return DQ_ENOMEM;
+  }
+  memcpy(b->key_type, ctx->info_type.data(), 4 * K);
+  memcpy(b->key_width, ctx->info_width.data(), 4 * K);
+  memcpy(b->key_base, ctx->info_base.data(), 8 * K);
+  if (cells > 0) {
+    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
+        {b->flags, ctx->i_flags.p, cells},        {b->n_values, ctx->i_nval.p, 4 * cells},
+        {b->val_off, ctx->i_off.p, 4 * cells},    {b->val_len, ctx->i_len.p, 4 * cells},
+        {b->ival, ctx->i_ival.p, 4 * nival},      {b->fval, ctx->i_fval.p, 8 * nfval}};
+    bool ok = true;
+    for (const auto& c : cp)
+      if (c.bytes) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
+      dq_info_batch_free(b);
+      RET(DQ_EDEVICE, "dq_vcf_info: device to host copy failed");
+    }
+  }
+  for (int64_t i = 0; i < nsplit; i++) b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
+  b->part_offset[nsplit] = n;
+  b->n_float_host = ctx->info_nhost;
+  *out = b;
+  return 0;
+}
+
+void dq_info_batch_free(dq_info_batch* b) {
+  if (!b) return;
+  free(b->key_type);
+  free(b->key_width);
+  free(b->key_base);
+  free(b->flags);
+  free(b->n_values);
+  free(b->val_off);
+  free(b->val_len);
+  free(b->ival);
+  free(b->fval);
+  free(b->part_offset);
+  free(b);
+}
+
 // TabixIndexCreator / BinningIndexBuilder (DESIGN.md "Building the .tbi"): data lines, their keys
 // and runs on the device (dq_text.hip), then the .bai kernels over the same key / voff / endp / pos
 // arrays; the host names the contigs, orders the bin headers and serialises.
@@ -4734,9 +4980,11 @@ int dq_checked_report(uint64_t words[4]) {
       words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
     }
   }
-  for (int u = 0; u < 3; u++) {  // and so do the SAM writer's unit and the VCF decodes' two
-    const uint64_t a = words[2],
-                   b = u == 0 ? dq::dq_chk_take_samw() : u == 1 ? dq::dq_chk_take_vcf() : dq::dq_chk_take_vcfgt();
+  for (int u = 0; u < 4; u++) {  // and so do the SAM writer's unit and the VCF decodes' three
+    const uint64_t a = words[2], b = u == 0   ? dq::dq_chk_take_samw()
+                                     : u == 1 ? dq::dq_chk_take_vcf()
+                                     : u == 2 ? dq::dq_chk_take_vcfgt()
+                                              : dq::dq_chk_take_vcfinfo();
     if (a == ~0ull || b == ~0ull) {
       words[2] = ~0ull;
     } else {

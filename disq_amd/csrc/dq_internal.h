@@ -47,8 +47,9 @@ enum : int {
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
   CHK_SAM = 15,      // SAM read and write (dq_sam.hip, dq_samw.hip share the bit): a line, size,
                      //     record-byte, line-byte or fix-up slot
-  CHK_VCF = 15,      // VCF site and genotype decode (dq_vcf.hip, dq_vcf_gt.hip share the bit): a line,
-                     //     column row, matrix cell, LDS offset slot, fix-up slot or site byte
+  CHK_VCF = 15,      // VCF site, genotype and INFO decode (dq_vcf.hip, dq_vcf_gt.hip, dq_vcf_info.hip
+                     //     share the bit): a line, column row, matrix or INFO cell, LDS offset slot,
+                     //     fix-up slot or site byte
 };
 #ifdef DQ_CHECKED
 namespace {
@@ -494,6 +495,49 @@ void launch_gt_check(GtIn in, unsigned long long* scal, hipStream_t s);
 void launch_gt_decode(GtIn in, GtCols out, int32_t P, int64_t* fix, int64_t fix_cap,
                       unsigned long long* scal, hipStream_t s);
 
+// ------------------------------------------------------------------ VCF INFO decode (dq_vcf_info.hip)
+struct InfoKeysDev {       // dqi::InfoKeys in device memory (dq_vcf_info_core.h), n <= 64
+  const uint64_t* hash;
+  const int32_t* idx;
+  const int32_t* id_off;
+  const uint8_t* ids;
+  const uint8_t* type;
+  const uint8_t* hflag;
+  int32_t n;
+};
+struct InfoIn {            // the kept variants of a text run and their column ends, as GtIn
+  const uint8_t* U;
+  int64_t ulen;
+  const int64_t* vstart;
+  const int32_t* vlen;
+  const int64_t* lidx;
+  int64_t total;
+  const int64_t* kept;
+  int64_t n;
+  const int32_t* col_end;  // INFO is [col_end[8 j + 6] + 1, col_end[8 j + 7]) of variant j's value
+  InfoKeysDev keys;
+};
+struct InfoCols {          // the arrays of dq_info_batch, key-major: cell (q, k) at q * n + k
+  uint8_t* flags;
+  int32_t* n_values;
+  int32_t* val_off;
+  int32_t* val_len;
+  int32_t* ival;
+  int64_t n_ival;
+  uint64_t* fval;          // the doubles' bits
+  int64_t n_fval;
+  const int64_t* key_base; // [K] in device memory
+  const int32_t* key_width;
+};
+// Check pass: scal[0] (all ones) takes the smallest dqi::info_error_key, scal[1] (zero) the count
+// of Float texts left to the host; scal[2] is the decode pass's; width[q] (one) takes the largest
+// value count of key q.
+void launch_info_check(InfoIn in, unsigned long long* scal, int32_t* width, hipStream_t s);
+// Decode pass: the columns; the host's Float texts appended to fix (5 words each: key, variant,
+// element, text offset in U, text length), counted in scal[2] (zero).
+void launch_info_decode(InfoIn in, InfoCols out, int64_t* fix, int64_t fix_cap, unsigned long long* scal,
+                        hipStream_t s);
+
 // ------------------------------------------------------------------ SAM writer (dq_samw.hip)
 struct SamwRefs {           // the header's reference names by index, see dq_samw_core.h
   const int32_t* name_off;  // n + 1 offsets into names
@@ -518,6 +562,7 @@ uint64_t dq_chk_take_sam();
 uint64_t dq_chk_take_samw();
 uint64_t dq_chk_take_vcf();
 uint64_t dq_chk_take_vcfgt();
+uint64_t dq_chk_take_vcfinfo();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

@@ -415,6 +415,28 @@ class GenotypesPartition:
         return len(self.flags)
 
 
+class InfoPartition:
+    """One partition's rows of the INFO columns (Context.vcf_info): keys (the ids), flags, n_values,
+    val_off and val_len shaped (K, rows), and values: per key its rows of the Integer or Float
+    column shaped (rows,) or (rows, W), None for a Flag or String key; row k belongs to the
+    partition's variant k."""
+    __slots__ = ("keys", "flags", "n_values", "val_off", "val_len", "values")
+
+    def __init__(self, g, lo, hi):
+        self.keys = list(g["keys"])
+        for k in ("flags", "n_values", "val_off", "val_len"):
+            setattr(self, k, g[k][:, lo:hi])
+        self.values = [None if v is None else v[lo:hi] for v in g["values"]]
+
+    def __len__(self):
+        return self.flags.shape[1]
+
+    def get(self, key):
+        """(flags, values) of one key by its id."""
+        q = self.keys.index(key.encode() if isinstance(key, str) else key)
+        return self.flags[q], self.values[q]
+
+
 class VariantsRDD:
     def __init__(self, partitions):
         self.partitions = partitions
@@ -430,10 +452,19 @@ class VariantsRDD:
 
 
 class HtsjdkVariantsRdd:
-    def __init__(self, header_lines, variants: VariantsRDD, genotypes=None):
+    def __init__(self, header_lines, variants: VariantsRDD, genotypes=None, info=None):
         self._header = header_lines
         self._variants = variants
         self._genotypes = genotypes
+        self._info = info
+
+    def getInfo(self):
+        """One InfoPartition per partition (read(info=[...])), else None."""
+        g = self._info
+        if g is None:
+            return None
+        po = g["part_offset"]
+        return [InfoPartition(g, int(po[p]), int(po[p + 1])) for p in range(len(po) - 1)]
 
     def getSampleNames(self):
         """The #CHROM line's sample names (read(genotypes=True)), else None."""
@@ -475,13 +506,17 @@ class HtsjdkVariantsRddStorage:
         return self
 
     def read(self, path: str, intervals: Optional[Sequence[Interval]] = None,
-             decode: bool = False, genotypes: bool = False) -> HtsjdkVariantsRdd:
+             decode: bool = False, genotypes: bool = False, info=None) -> HtsjdkVariantsRdd:
         """decode: each partition holds VariantSite rows (the device's VCFCodec.decode, SITES
         export: only the first eight columns' bytes cross to the host) instead of line bytes.
         genotypes (with decode): the sample columns decoded on the device as well
-        (dq_vcf_genotypes); the rdd then answers getSampleNames() and getGenotypes()."""
+        (dq_vcf_genotypes); the rdd then answers getSampleNames() and getGenotypes().
+        info (with decode): INFO keys, names or (name, type) pairs, decoded on the device into
+        typed columns (dq_vcf_info); the rdd then answers getInfo()."""
         if genotypes and not decode:
             raise ValueError("genotypes=True needs decode=True")
+        if info is not None and not decode:
+            raise ValueError("info=[...] needs decode=True")
         if not (path.endswith(".gz") or path.endswith(".bgz")):
             raise ValueError(f"{path}: the GPU text path reads BGZF-compressed VCF (.vcf.gz/.vcf.bgz)")
         with _lib.Context(split_size=self._split_size, device=self._device) as ctx:
@@ -496,8 +531,9 @@ class HtsjdkVariantsRddStorage:
                                         for iv in intervals])
             b = ctx.vcf_read(_lib.VCF_EXPORT_SITES) if decode else ctx.text_read(True)
             g = ctx.vcf_genotypes() if genotypes else None
+            i = ctx.vcf_info(list(info)) if info is not None else None
         if decode:
-            return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(variant_sites(b)), g)
+            return HtsjdkVariantsRdd(vcf_header_lines(path), VariantsRDD(variant_sites(b)), g, i)
         d, do, ln, po = b["data"], b["data_offset"], b["line_len"], b["part_offset"]
         parts = [VariantsPartition(bytes(d[do[k]:do[k] + ln[k]]) for k in range(po[p], po[p + 1]))
                  for p in range(len(po) - 1)]

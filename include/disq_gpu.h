@@ -32,6 +32,8 @@
  *     filter and the overlap filter (D/impl/formats/vcf/VcfSource.java:113)    dq_vcf_read
  *   AbstractVCFCodec.createGenotypeMap, what VariantContext.getGenotypes() runs on the text
  *     LazyGenotypesContext kept, over the variants VcfSource.getVariants hands out  dq_vcf_genotypes
+ *   AbstractVCFCodec.parseInfo for the keys a consumer asks of VariantContext.getAttribute /
+ *     getAttributeAsInt / getAttributeAsDouble / hasAttribute, over the same variants  dq_vcf_info
  *
  * Error mapping (Java side): DQ_EIO -> IOException; DQ_EFORMAT -> htsjdk SAMFormatException;
  * DQ_EINVAL -> IllegalArgumentException; DQ_EDEVICE / DQ_ENOMEM -> RuntimeException.
@@ -499,6 +501,63 @@ typedef struct dq_genotype_batch {
 int dq_vcf_genotypes_run(dq_ctx* ctx, dq_stats* stats);
 int dq_vcf_genotypes(dq_ctx* ctx, dq_genotype_batch** out);
 void dq_genotype_batch_free(dq_genotype_batch* b);
+
+/* ---- VCF INFO decode: parseInfo projected onto keys -----------
+ * The INFO column of the variants of dq_vcf_read on the same context -- the same lines in the same
+ * order and partitions, after the same tabix pruning and overlap filter -- decoded on the device
+ * into one typed column block per requested key (1 to 64 keys): what htsjdk's
+ * AbstractVCFCodec.parseInfo leaves in the attribute map for those keys.  The rules are DESIGN.md
+ * section 17.  The column splits on ';', a key is the text before a piece's first '=' and matches a
+ * requested id byte for byte; the first piece of a key is decoded and a later one only sets
+ * DQ_INFO_REPEATED.  "key=" and "key=." are present without a value; a key the header types as Flag
+ * with the value "0" is absent (htsjdk's "DB=0").  An explicit type overrides the header's only for
+ * how values are converted.  INTEGER elements are '.' (missing) or [-+]?[0-9]+ in int32; FLOAT
+ * elements are '.', the QUAL grammar, NaN, Infinity, +Infinity or -Infinity; an empty element is an
+ * error for both; FLAG and STRING values are not converted, their span (val_off, val_len, into the
+ * line's value, so into a SITES or LINES export of dq_vcf_read) is the access path.
+ * Both calls run the site decode first when the context has not (its errors come first,
+ * unchanged); then only the variants handed out are checked: the first failing value gives
+ * DQ_EFORMAT and dq_last_error "VCF line <k>: INFO <id>", k as dq_vcf_read counts lines and the
+ * lowest offender, then the lowest index in keys.  dq_vcf_read, dq_vcf_genotypes and the dq_text_*
+ * calls work on the same context afterwards.  DQ_EINVAL: a BAM or SAM context, no open file,
+ * n_keys < 1 or > 64, an id that is empty or holds ';', '=', ',', a TAB or a space, the same id
+ * twice, an unknown type.  DQ_ENOMEM: the columns do not fit.
+ * Not done: Number= checks, VCF 4.3 percent-decoding, the last-wins order of htsjdk's map, keys
+ * that were not asked for, copies of String values, BCF. */
+#define DQ_INFO_AUTO 0      /* take Type from the header's ##INFO line; no such line: STRING */
+#define DQ_INFO_FLAG 1
+#define DQ_INFO_INTEGER 2
+#define DQ_INFO_FLOAT 3
+#define DQ_INFO_STRING 4    /* also Character: the span only */
+/* cell flags */
+#define DQ_INFO_PRESENT 1   /* the key is in the line's INFO map */
+#define DQ_INFO_HAS_VALUE 2 /* it has a value text that is not empty and not "." */
+#define DQ_INFO_REPEATED 4  /* the key occurs again later in the line (the first is decoded) */
+#define DQ_INFO_I_MISSING INT32_MIN
+#define DQ_INFO_F_MISSING_BITS 0x7ff8000000000001ULL /* a quiet NaN with payload 1; "NaN" itself is 0x7ff8000000000000 */
+typedef struct dq_info_key { const char* id; int32_t type; int32_t reserved; } dq_info_key;
+typedef struct dq_info_batch {
+  int64_t n_variants;          /* = dq_vcf_read's; row k is its variant k */
+  int32_t n_keys;              /* K */
+  int32_t reserved;
+  int32_t* key_type;           /* [K] the resolved DQ_INFO_* (never AUTO) */
+  int32_t* key_width;          /* [K] W_q: the largest value count of key q over the rows, at least 1 */
+  int64_t* key_base;           /* [K] element offset of key q's block in ival (INTEGER) or fval (FLOAT), -1 otherwise */
+  uint8_t* flags;              /* [K * n_variants], key-major: cell (q, k) at q * n_variants + k */
+  int32_t* n_values;           /* [K * n_variants] ',' pieces of the value text; 0 without HAS_VALUE */
+  int32_t* val_off;            /* [K * n_variants] offset of the value text in the line's value, -1 when absent */
+  int32_t* val_len;            /* [K * n_variants] */
+  int32_t* ival;  int64_t n_ival;  /* value j of (q, k) at key_base[q] + k * W_q + j; INT32_MIN = missing */
+  double*  fval;  int64_t n_fval;  /* the same; NaN with payload 1 = missing (DQ_INFO_F_MISSING_BITS) */
+  int64_t n_partitions; int64_t* part_offset;   /* as dq_vcf_read */
+  int64_t n_float_host;        /* Float texts off the device's exact path, converted by the host's strtod */
+} dq_info_batch;
+/* The site decode when the context has not run it, then the INFO check and decode passes for these
+ * keys; the columns stay in HBM.  stats: dq_vcf_run's, with the device time of the two INFO passes
+ * added to ms_records and to ms_total. */
+int dq_vcf_info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_stats* stats);
+int dq_vcf_info(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_info_batch** out);
+void dq_info_batch_free(dq_info_batch* b);
 
 /* ---- SAM text: SamSource.getReads -----------------------------
  * An uncompressed SAM file read as Disq reads it (D/impl/formats/sam/SamSource.java:36-77): Hadoop
