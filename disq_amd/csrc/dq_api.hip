@@ -165,7 +165,7 @@ struct dq_ctx {
   std::vector<std::string> vcf_contigs;
   DevBuf v_ctg, v_scal, v_fix, v_contig, v_pos, v_end, v_flags, v_qual, v_colend, v_nalt, v_nfilter,
       v_ninfo, v_nsample, v_sitelen;
-  dq::VcfContigs vcf_ctg{};
+  dqt::NameTable vcf_ctg{};
   int64_t vcf_nqual_host = 0;
   double vcf_ms = 0;
   // VCF genotype decode (dq_vcf_genotypes*) behind the site decode: the #CHROM line's sample names,
@@ -194,7 +194,7 @@ struct dq_ctx {
   int32_t sam_bom = 0;              // the text starts with a UTF-8 BOM
   unsigned long long sam_init[4] = {~0ull, 0, 0, 0};  // first failing line | undecided | fix-ups
   DevBuf s_ls, s_vs, s_vl, s_splits, s_status, s_size, s_fix, s_refs, sam_rec;
-  dq::SamRefs sam_refs{};
+  dqt::NameTable sam_refs{};
   // SAM writer (dq_sam_write*): the uploaded records and offsets, per record status / line size /
   // line offset, the reference names, the text (w_len bytes)
   DevBuf w_in, w_off, w_status, w_size, w_loff, w_refs, w_scal, w_out;
@@ -2150,6 +2150,87 @@ static int run_span(dq_ctx* ctx, const dq_traversal* tr, dq_stats* out) {
   }
 }
 
+// ------------------------------------------------------------------ shared by the text decoders
+// A name table (dq_text_core.h) into one device buffer: hashes | name offsets | indices | name bytes
+// (and 8 bytes of slack) | tail -- `tail_n` bytes of the caller's own behind the table, at *dev_tail.
+static int upload_name_table(dq_ctx* ctx, DevBuf& b, const dqt::NameTableHost& T, dqt::NameTable* dev,
+                             const uint8_t* tail = nullptr, size_t tail_n = 0, const uint8_t** dev_tail = nullptr) {
+  const size_t nr = T.idx.size();
+  const size_t o_hash = 0, o_off = o_hash + 8 * nr, o_idx = o_off + 4 * (nr + 1), o_names = o_idx + 4 * nr,
+               o_tail = o_names + T.names.size() + 8;
+  std::vector<uint8_t> buf(o_tail + tail_n);
+  if (nr) {
+    memcpy(&buf[o_hash], T.hash.data(), 8 * nr);
+    memcpy(&buf[o_idx], T.idx.data(), 4 * nr);
+  }
+  memcpy(&buf[o_off], T.name_off.data(), 4 * (nr + 1));
+  memcpy(&buf[o_names], T.names.data(), T.names.size());
+  if (tail_n) memcpy(&buf[o_tail], tail, tail_n);
+  int rc;
+  if ((rc = ensure_all(ctx, b, buf.size()))) return rc;
+  HIPCHK(hipMemcpy(b.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  const uint8_t* d = b.as<uint8_t>();
+  *dev = dqt::NameTable{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx), (const int32_t*)(d + o_off),
+                        d + o_names, (int32_t)nr};
+  if (dev_tail) *dev_tail = d + o_tail;
+  return 0;
+}
+
+// ensure, and say DQ_ENOMEM with `what` when the device has no room
+static int ensure_or_nomem(dq_ctx* ctx, DevBuf& b, size_t bytes, const char* what) {
+  const hipError_t e = b.ensure(bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    RET(DQ_ENOMEM, what);
+  }
+  HIPCHK(e);
+  return 0;
+}
+
+// The host's fix-up pass behind a decode pass: the texts the device left undecided (normally none),
+// each converted by the C library and its value copied back.  d_cnt: the pass's count of entries,
+// which must equal `expect`, the earlier pass's count (at_most: not exceed it); d_list: the entries
+// of `width` words, the last two a text's offset and length in d_text[0, text_len); *n_done: the
+// count.  conv(w, text, &V) checks the entry's leading words w, converts and fills V; false refuses
+// the entry.  `pass` opens both DQ_EDEVICE messages.
+struct FixValue {
+  void* dst;     // device address of the value
+  size_t bytes;  // 4 or 8
+  union {
+    float f;
+    double d;
+    int32_t i;
+  } v;
+};
+template <class Conv>
+static int host_fixups(dq_ctx* ctx, const unsigned long long* d_cnt, int64_t expect, bool at_most,
+                       const void* d_list, size_t width, const uint8_t* d_text, int64_t text_len,
+                       const std::string& pass, const char* count_differs, int64_t* n_done, Conv conv) {
+  unsigned long long cnt = 0;
+  HIPCHK(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->s));
+  HIPCHK(hipStreamSynchronize(ctx->s));
+  if (at_most ? (int64_t)cnt > expect : (int64_t)cnt != expect) RET(DQ_EDEVICE, pass + ": " + count_differs);
+  if (n_done) *n_done = (int64_t)cnt;
+  if (cnt == 0) return 0;
+  std::vector<int64_t> ent(width * (size_t)cnt);
+  HIPCHK(hipMemcpy(ent.data(), d_list, 8 * ent.size(), hipMemcpyDeviceToHost));
+  std::string txt;
+  for (size_t e = 0; e < (size_t)cnt; e++) {
+    const int64_t* w = &ent[width * e];
+    const int64_t ta = w[width - 2], tn = w[width - 1];
+    FixValue V{};
+    bool ok = ta >= 0 && tn > 0 && ta + tn <= text_len;
+    if (ok) {
+      txt.assign((size_t)tn, '\0');
+      HIPCHK(hipMemcpy(&txt[0], d_text + ta, (size_t)tn, hipMemcpyDeviceToHost));
+      ok = conv(w, txt.c_str(), &V);
+    }
+    if (!ok) RET(DQ_EDEVICE, pass + ": bad fix-up entry");
+    HIPCHK(hipMemcpy(V.dst, &V.v, V.bytes, hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ SAM text path (row f7)
 // SamSource.getReads over the resident text (ctx->cbuf(), flen bytes and the opens' zero pad; nothing
 // is put in U): terminators, line table, partitions, size pass + scan, encode pass, float fix-ups,
@@ -2259,24 +2340,17 @@ static int sam_run(dq_ctx* ctx) {
                     ctx->s_size.as<int32_t>(), ctx->sam_rec.as<uint8_t>(), ctx->soa(),
                     ctx->s_fix.as<int64_t>(), nund, d_scal + 2, s);
   // ---- float fix-ups: the texts sam_parse_float left undecided, converted by strtof (normally none)
-  if (nund > 0) {
-    unsigned long long cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if ((int64_t)cnt != nund) RET(DQ_EDEVICE, "SAM encode pass: the fix-up count differs from the size pass's");
-    std::vector<int64_t> ent(3 * (size_t)nund);
-    HIPCHK(hipMemcpy(ent.data(), ctx->s_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
-    std::string txt;
-    for (int64_t e = 0; e < nund; e++) {
-      const int64_t oo = ent[3 * (size_t)e], ta = ent[3 * (size_t)e + 1], tn = ent[3 * (size_t)e + 2];
-      if (oo < 0 || oo + 4 > total || ta < 0 || tn <= 0 || ta + tn > L)
-        RET(DQ_EDEVICE, "SAM encode pass: bad fix-up entry");
-      txt.assign((size_t)tn, '\0');
-      HIPCHK(hipMemcpy(&txt[0], T + ta, (size_t)tn, hipMemcpyDeviceToHost));
-      const float f = strtof(txt.c_str(), nullptr);
-      HIPCHK(hipMemcpy(ctx->sam_rec.as<uint8_t>() + oo, &f, 4, hipMemcpyHostToDevice));
-    }
-  }
+  if (nund > 0 &&
+      (rc = host_fixups(ctx, d_scal + 2, nund, false, ctx->s_fix.p, 3, T, L, "SAM encode pass",
+                        "the fix-up count differs from the size pass's", nullptr,
+                        [&](const int64_t* w, const char* text, FixValue* V) {
+                          if (w[0] < 0 || w[0] + 4 > total) return false;
+                          V->dst = ctx->sam_rec.as<uint8_t>() + w[0];
+                          V->bytes = 4;
+                          V->v.f = strtof(text, nullptr);
+                          return true;
+                        })))
+    return rc;
   // ---- hashes (the BAM path's hash of a record's 4 + block_size bytes) and partition digests
   launch_span_hash(ctx->sam_rec.as<uint8_t>(), ctx->rec_lin.as<int64_t>(), ctx->s_size.as<int32_t>(), n,
                    ctx->f_hash.as<uint64_t>(), s);
@@ -2328,26 +2402,9 @@ static int sam_set_header(dq_ctx* ctx, const uint8_t* t, int64_t n, bool whole) 
   ctx->ref_name = H.names;
   ctx->ref_len = H.lens;
   ctx->sam_bom = n >= 3 && t[0] == 0xEF && t[1] == 0xBB && t[2] == 0xBF;
-  dqs::RefTableHost R;
-  dqs::sam_ref_table_build(H.names, &R);
-  // one buffer: hashes | name offsets | indices | name bytes
-  const size_t nr = H.names.size();
-  const size_t o_hash = 0, o_off = o_hash + 8 * nr, o_idx = o_off + 4 * (nr + 1),
-               o_names = o_idx + 4 * nr, bytes = o_names + R.names.size();
-  std::vector<uint8_t> buf(bytes + 8);
-  if (nr) {
-    memcpy(&buf[o_hash], R.hash.data(), 8 * nr);
-    memcpy(&buf[o_idx], R.idx.data(), 4 * nr);
-  }
-  memcpy(&buf[o_off], R.name_off.data(), 4 * (nr + 1));
-  memcpy(&buf[o_names], R.names.data(), R.names.size());
-  int rc;
-  if ((rc = ensure_all(ctx, ctx->s_refs, buf.size()))) return rc;
-  HIPCHK(hipMemcpy(ctx->s_refs.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  const uint8_t* d = ctx->s_refs.as<uint8_t>();
-  ctx->sam_refs = SamRefs{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
-                          (const int32_t*)(d + o_off), d + o_names, (int32_t)nr};
-  return 0;
+  dqt::NameTableHost R;
+  dqt::name_table_build(H.names, &R);
+  return upload_name_table(ctx, ctx->s_refs, R, &ctx->sam_refs);
 }
 
 // ------------------------------------------------------------------ opening inputs
@@ -3972,25 +4029,10 @@ static int vcf_header(dq_ctx* ctx) {
   ctx->vcf_samples.clear();
   if (H.G) dqg::gt_header_samples(pre.data(), pre_n, &ctx->vcf_samples);
   dqi::info_header_types(pre.data(), pre_n, &ctx->vcf_info_types);
-  dqv::ContigTableHost R;
-  dqv::vcf_contig_table_build(H.contigs, &R);
-  // one buffer: hashes | name offsets | indices | name bytes
-  const size_t nr = H.contigs.size();
-  const size_t o_hash = 0, o_off = o_hash + 8 * nr, o_idx = o_off + 4 * (nr + 1),
-               o_names = o_idx + 4 * nr, bytes = o_names + R.names.size();
-  std::vector<uint8_t> buf(bytes + 8);
-  if (nr) {
-    memcpy(&buf[o_hash], R.hash.data(), 8 * nr);
-    memcpy(&buf[o_idx], R.idx.data(), 4 * nr);
-  }
-  memcpy(&buf[o_off], R.name_off.data(), 4 * (nr + 1));
-  memcpy(&buf[o_names], R.names.data(), R.names.size());
+  dqt::NameTableHost R;
+  dqt::name_table_build(H.contigs, &R);
   int rc;
-  if ((rc = ensure_all(ctx, ctx->v_ctg, buf.size()))) return rc;
-  HIPCHK(hipMemcpy(ctx->v_ctg.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  const uint8_t* d = ctx->v_ctg.as<uint8_t>();
-  ctx->vcf_ctg = VcfContigs{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
-                            (const int32_t*)(d + o_off), d + o_names, (int32_t)nr};
+  if ((rc = upload_name_table(ctx, ctx->v_ctg, R, &ctx->vcf_ctg))) return rc;
   ctx->vcf_G = H.G ? 1 : 0;
   ctx->vcf_contigs = H.contigs;
   ctx->vcf_hdr = true;
@@ -4002,6 +4044,13 @@ static VcfCols vcf_cols(dq_ctx* ctx) {
                  ctx->v_flags.as<uint32_t>(), ctx->v_qual.as<double>(),     ctx->v_colend.as<int32_t>(),
                  ctx->v_nalt.as<int32_t>(),   ctx->v_nfilter.as<int32_t>(), ctx->v_ninfo.as<int32_t>(),
                  ctx->v_nsample.as<int32_t>(), ctx->v_sitelen.as<int32_t>()};
+}
+
+// the kept variants of the text run and the site decode's column ends, for the passes behind it
+static VcfLines vcf_lines(dq_ctx* ctx) {
+  return VcfLines{ctx->U.as<uint8_t>(),     ctx->ulen,    ctx->t_vs.as<int64_t>(),   ctx->t_vl.as<int32_t>(),
+                  ctx->t_idx.as<int64_t>(), ctx->t_total, ctx->t_kept.as<int64_t>(), ctx->t_nkept,
+                  ctx->v_colend.as<int32_t>()};
 }
 
 static int vcf_run(dq_ctx* ctx) {
@@ -4047,25 +4096,19 @@ static int vcf_run(dq_ctx* ctx) {
                     ctx->t_kept.as<int64_t>(), n, ctx->vcf_G, ctx->vcf_ctg, vcf_cols(ctx),
                     ctx->v_fix.as<int64_t>(), nund, d_scal + 2, s);
   HIPCHK(hipEventRecord(ctx->ev[11], s));
-  unsigned long long cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if ((int64_t)cnt > nund) RET(DQ_EDEVICE, "VCF decode pass: more undecided QUAL texts than the validate pass counted");
   // ---- QUAL fix-ups: the texts off the exact fast path, converted by strtod (normally none)
-  if (cnt > 0) {
-    std::vector<int64_t> ent(3 * (size_t)cnt);
-    HIPCHK(hipMemcpy(ent.data(), ctx->v_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
-    std::string txt;
-    for (size_t e = 0; e < (size_t)cnt; e++) {
-      const int64_t j = ent[3 * e], ta = ent[3 * e + 1], tn = ent[3 * e + 2];
-      if (j < 0 || j >= n || ta < 0 || tn <= 0 || ta + tn > ulen) RET(DQ_EDEVICE, "VCF decode pass: bad fix-up entry");
-      txt.assign((size_t)tn, '\0');
-      HIPCHK(hipMemcpy(&txt[0], U + ta, (size_t)tn, hipMemcpyDeviceToHost));
-      const double q = strtod(txt.c_str(), nullptr);
-      HIPCHK(hipMemcpy(ctx->v_qual.as<double>() + j, &q, 8, hipMemcpyHostToDevice));
-    }
-  }
-  ctx->vcf_nqual_host = (int64_t)cnt;
+  int64_t cnt = 0;
+  if ((rc = host_fixups(ctx, d_scal + 2, nund, true, ctx->v_fix.p, 3, U, ulen, "VCF decode pass",
+                        "more undecided QUAL texts than the validate pass counted", &cnt,
+                        [&](const int64_t* w, const char* text, FixValue* V) {
+                          if (w[0] < 0 || w[0] >= n) return false;
+                          V->dst = ctx->v_qual.as<double>() + w[0];
+                          V->bytes = 8;
+                          V->v.d = strtod(text, nullptr);
+                          return true;
+                        })))
+    return rc;
+  ctx->vcf_nqual_host = cnt;
   ctx->vcf_ms = (double)ev_ms(ctx->ev[8], ctx->ev[9]) + (double)ev_ms(ctx->ev[10], ctx->ev[11]);
   ctx->vcf_gen = ctx->text_gen;
   return 0;
@@ -4217,16 +4260,6 @@ void dq_variant_batch_free(dq_variant_batch* b) {
 // ---- VCF genotype decode (row f10): AbstractVCFCodec.createGenotypeMap over the variants of the
 // site decode.  The check and decode passes of dq_vcf_gt.hip run on the
 // columns vcf_run left in HBM; the matrix stays there.
-static int gt_ensure(dq_ctx* ctx, DevBuf& b, size_t bytes) {
-  const hipError_t e = b.ensure(bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    RET(DQ_ENOMEM, "the genotype matrix does not fit in device memory");
-  }
-  HIPCHK(e);
-  return 0;
-}
-
 static int gt_run(dq_ctx* ctx) {
   int rc = vcf_run(ctx);
   if (rc) return rc;
@@ -4239,10 +4272,7 @@ static int gt_run(dq_ctx* ctx) {
   if (S > 0 && n > 0) {
     if (S > INT32_MAX || n > (INT64_MAX >> 12) / S) RET(DQ_ENOMEM, "the genotype matrix does not fit in device memory");
     const int64_t cells = n * S;
-    const dq::GtIn in{ctx->U.as<uint8_t>(),       ctx->ulen,          ctx->t_vs.as<int64_t>(),
-                      ctx->t_vl.as<int32_t>(),    ctx->t_idx.as<int64_t>(), ctx->t_total,
-                      ctx->t_kept.as<int64_t>(),  n,                  ctx->v_colend.as<int32_t>(),
-                      ctx->v_nalt.as<int32_t>(),  ctx->v_nsample.as<int32_t>(), (int32_t)S};
+    const dq::GtIn in{vcf_lines(ctx), ctx->v_nalt.as<int32_t>(), ctx->v_nsample.as<int32_t>(), (int32_t)S};
     // ---- check: first offender | largest ploidy | GQ texts for the host (| the decode pass's list)
     if ((rc = ensure_all(ctx, ctx->g_scal, 64))) return rc;
     unsigned long long* d_scal = ctx->g_scal.as<unsigned long long>();
@@ -4264,36 +4294,31 @@ static int gt_run(dq_ctx* ctx) {
     const int32_t P = (int32_t)std::max<unsigned long long>(1, std::min<unsigned long long>(sc[1], dqg::GT_MAX_PLOIDY));
     const int64_t nhost = (int64_t)sc[2];
     // ---- decode
-    if ((rc = gt_ensure(ctx, ctx->g_flags, (size_t)cells)) || (rc = gt_ensure(ctx, ctx->g_ploidy, (size_t)cells)) ||
-        (rc = gt_ensure(ctx, ctx->g_allele, 2 * (size_t)cells * (size_t)P)) ||
-        (rc = gt_ensure(ctx, ctx->g_gq, 4 * (size_t)cells)) || (rc = gt_ensure(ctx, ctx->g_dp, 4 * (size_t)cells)) ||
-        (rc = gt_ensure(ctx, ctx->g_off, 4 * (size_t)cells)) ||
-        (rc = gt_ensure(ctx, ctx->g_fix, 24 * (size_t)std::max<int64_t>(1, nhost))))
+    const char* nomem = "the genotype matrix does not fit in device memory";
+    if ((rc = ensure_or_nomem(ctx, ctx->g_flags, (size_t)cells, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_ploidy, (size_t)cells, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_allele, 2 * (size_t)cells * (size_t)P, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_gq, 4 * (size_t)cells, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_dp, 4 * (size_t)cells, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_off, 4 * (size_t)cells, nomem)) ||
+        (rc = ensure_or_nomem(ctx, ctx->g_fix, 24 * (size_t)std::max<int64_t>(1, nhost), nomem)))
       return rc;
     const dq::GtCols out{ctx->g_flags.as<uint8_t>(), ctx->g_ploidy.as<uint8_t>(), ctx->g_allele.as<int16_t>(),
                          ctx->g_gq.as<int32_t>(),    ctx->g_dp.as<int32_t>(),     ctx->g_off.as<int32_t>()};
     HIPCHK(hipEventRecord(ctx->ev[14], s));
     dq::launch_gt_decode(in, out, P, ctx->g_fix.as<int64_t>(), nhost, d_scal, s);
     HIPCHK(hipEventRecord(ctx->ev[15], s));
-    unsigned long long cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, d_scal + 3, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if ((int64_t)cnt != nhost) RET(DQ_EDEVICE, "VCF genotype decode pass: its GQ texts for the host differ from the check pass's count");
     // ---- GQ fix-ups: the texts off the digit path, strtod and Java's rounding (normally none)
-    if (cnt > 0) {
-      std::vector<int64_t> ent(3 * (size_t)cnt);
-      HIPCHK(hipMemcpy(ent.data(), ctx->g_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
-      std::string txt;
-      for (size_t e = 0; e < (size_t)cnt; e++) {
-        const int64_t c = ent[3 * e], ta = ent[3 * e + 1], tn = ent[3 * e + 2];
-        if (c < 0 || c >= cells || ta < 0 || tn <= 0 || ta + tn > ctx->ulen)
-          RET(DQ_EDEVICE, "VCF genotype decode pass: bad fix-up entry");
-        txt.assign((size_t)tn, '\0');
-        HIPCHK(hipMemcpy(&txt[0], ctx->U.as<uint8_t>() + ta, (size_t)tn, hipMemcpyDeviceToHost));
-        const int32_t q = dqg::gt_round_gq(strtod(txt.c_str(), nullptr));
-        HIPCHK(hipMemcpy(ctx->g_gq.as<int32_t>() + c, &q, 4, hipMemcpyHostToDevice));
-      }
-    }
+    if ((rc = host_fixups(ctx, d_scal + 3, nhost, false, ctx->g_fix.p, 3, ctx->U.as<uint8_t>(), ctx->ulen,
+                          "VCF genotype decode pass", "its GQ texts for the host differ from the check pass's count",
+                          nullptr, [&](const int64_t* w, const char* text, FixValue* V) {
+                            if (w[0] < 0 || w[0] >= cells) return false;
+                            V->dst = ctx->g_gq.as<int32_t>() + w[0];
+                            V->bytes = 4;
+                            V->v.i = dqg::gt_round_gq(strtod(text, nullptr));
+                            return true;
+                          })))
+      return rc;
     ctx->gt_P = P;
     ctx->gt_nhost = nhost;
     ctx->gt_ms = (double)ev_ms(ctx->ev[12], ctx->ev[13]) + (double)ev_ms(ctx->ev[14], ctx->ev[15]);
@@ -4390,16 +4415,6 @@ void dq_genotype_batch_free(dq_genotype_batch* b) {
 // ---- VCF INFO decode (row f11): AbstractVCFCodec.parseInfo over the variants of the site decode,
 // projected onto the caller's keys.  The check and decode passes of dq_vcf_info.hip (DESIGN.md
 // section 17) run on the col_end vcf_run left in HBM; the columns stay there.
-static int info_ensure(dq_ctx* ctx, DevBuf& b, size_t bytes) {
-  const hipError_t e = b.ensure(std::max<size_t>(8, bytes));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    RET(DQ_ENOMEM, "the INFO columns do not fit in device memory");
-  }
-  HIPCHK(e);
-  return 0;
-}
-
 static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
   if (ctx->sam_mode || !ctx->text_mode) RET(DQ_EINVAL, "not a text context (dq_text_open_*)");
   if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
@@ -4423,29 +4438,14 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
     RET(DQ_EINVAL, std::string("dq_vcf_info: ") + why);
   hipStream_t s = ctx->s;
   const int64_t n = ctx->t_nkept, K = n_keys;
-  // one buffer: hashes | sorted indices | id offsets | types | header Flag marks | id bytes
-  const size_t o_hash = 0, o_idx = 8 * (size_t)K, o_off = o_idx + 4 * (size_t)K, o_type = o_off + 4 * (size_t)(K + 1),
-               o_hflag = o_type + (size_t)K, o_ids = o_hflag + (size_t)K;
-  std::vector<uint8_t> buf(o_ids + KT.ids.size() + 8);
-  memcpy(&buf[o_hash], KT.hash.data(), 8 * (size_t)K);
-  memcpy(&buf[o_idx], KT.idx.data(), 4 * (size_t)K);
-  memcpy(&buf[o_off], KT.id_off.data(), 4 * (size_t)(K + 1));
-  memcpy(&buf[o_type], KT.type.data(), (size_t)K);
-  memcpy(&buf[o_hflag], KT.hflag.data(), (size_t)K);
-  memcpy(&buf[o_ids], KT.ids.data(), KT.ids.size());
-  if ((rc = ensure_all(ctx, ctx->i_keys, buf.size())) || (rc = ensure_all(ctx, ctx->i_scal, 512)) ||
-      (rc = ensure_all(ctx, ctx->i_meta, 768)))
-    return rc;
+  if ((rc = ensure_all(ctx, ctx->i_scal, 512)) || (rc = ensure_all(ctx, ctx->i_meta, 768))) return rc;
   HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(hipMemcpy(ctx->i_keys.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  const uint8_t* d = ctx->i_keys.as<uint8_t>();
-  const dq::InfoIn in{ctx->U.as<uint8_t>(),      ctx->ulen,
-                      ctx->t_vs.as<int64_t>(),   ctx->t_vl.as<int32_t>(),
-                      ctx->t_idx.as<int64_t>(),  ctx->t_total,
-                      ctx->t_kept.as<int64_t>(), n,
-                      ctx->v_colend.as<int32_t>(),
-                      dq::InfoKeysDev{(const uint64_t*)(d + o_hash), (const int32_t*)(d + o_idx),
-                                      (const int32_t*)(d + o_off), d + o_ids, d + o_type, d + o_hflag, (int32_t)K}};
+  // the key table, and behind it the types | the header's Flag marks
+  std::vector<uint8_t> marks(KT.type);
+  marks.insert(marks.end(), KT.hflag.begin(), KT.hflag.end());
+  dq::InfoIn in{vcf_lines(ctx), {}, nullptr, nullptr};
+  if ((rc = upload_name_table(ctx, ctx->i_keys, KT.tab, &in.keys, marks.data(), marks.size(), &in.key_type))) return rc;
+  in.key_hflag = in.key_type + K;
   // ---- check: first offender | Float texts for the host | the decode pass's list; widths behind
   struct {
     unsigned long long sc[8];
@@ -4490,10 +4490,12 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
   }
   // ---- decode
   const size_t cells = (size_t)K * (size_t)n;
-  if ((rc = info_ensure(ctx, ctx->i_flags, cells)) || (rc = info_ensure(ctx, ctx->i_nval, 4 * cells)) ||
-      (rc = info_ensure(ctx, ctx->i_off, 4 * cells)) || (rc = info_ensure(ctx, ctx->i_len, 4 * cells)) ||
-      (rc = info_ensure(ctx, ctx->i_ival, 4 * (size_t)nival)) || (rc = info_ensure(ctx, ctx->i_fval, 8 * (size_t)nfval)) ||
-      (rc = info_ensure(ctx, ctx->i_fix, 40 * (size_t)std::max<int64_t>(1, nhost))))
+  const char* nomem = "the INFO columns do not fit in device memory";
+  const auto ensure8 = [&](DevBuf& b, size_t bytes) { return ensure_or_nomem(ctx, b, std::max<size_t>(8, bytes), nomem); };
+  if ((rc = ensure8(ctx->i_flags, cells)) || (rc = ensure8(ctx->i_nval, 4 * cells)) ||
+      (rc = ensure8(ctx->i_off, 4 * cells)) || (rc = ensure8(ctx->i_len, 4 * cells)) ||
+      (rc = ensure8(ctx->i_ival, 4 * (size_t)nival)) || (rc = ensure8(ctx->i_fval, 8 * (size_t)nfval)) ||
+      (rc = ensure8(ctx->i_fix, 40 * (size_t)std::max<int64_t>(1, nhost))))
     return rc;
   const dq::InfoCols out{ctx->i_flags.as<uint8_t>(), ctx->i_nval.as<int32_t>(), ctx->i_off.as<int32_t>(),
                          ctx->i_len.as<int32_t>(),   ctx->i_ival.as<int32_t>(), nival,
@@ -4502,26 +4504,20 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
   HIPCHK(hipEventRecord(ctx->ev[18], s));
   dq::launch_info_decode(in, out, ctx->i_fix.as<int64_t>(), nhost, d_scal, s);
   HIPCHK(hipEventRecord(ctx->ev[19], s));
-  unsigned long long cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, d_scal + 2, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if ((int64_t)cnt != nhost) RET(DQ_EDEVICE, "VCF INFO decode pass: its Float texts for the host differ from the check pass's count");
   // ---- Float fix-ups: the texts off the exact path, converted by strtod (normally none)
-  if (cnt > 0) {
-    std::vector<int64_t> ent(5 * (size_t)cnt);
-    HIPCHK(hipMemcpy(ent.data(), ctx->i_fix.p, 8 * ent.size(), hipMemcpyDeviceToHost));
-    std::string txt;
-    for (size_t e = 0; e < (size_t)cnt; e++) {
-      const int64_t q = ent[5 * e], k = ent[5 * e + 1], j = ent[5 * e + 2], ta = ent[5 * e + 3], tn = ent[5 * e + 4];
-      if (q < 0 || q >= K || type[(size_t)q] != dqi::INFO_FLOAT || k < 0 || k >= n || j < 0 || j >= width[(size_t)q] ||
-          ta < 0 || tn <= 0 || ta + tn > ctx->ulen)
-        RET(DQ_EDEVICE, "VCF INFO decode pass: bad fix-up entry");
-      txt.assign((size_t)tn, '\0');
-      HIPCHK(hipMemcpy(&txt[0], ctx->U.as<uint8_t>() + ta, (size_t)tn, hipMemcpyDeviceToHost));
-      const double v = strtod(txt.c_str(), nullptr);
-      HIPCHK(hipMemcpy(ctx->i_fval.as<double>() + base[(size_t)q] + k * width[(size_t)q] + j, &v, 8, hipMemcpyHostToDevice));
-    }
-  }
+  if ((rc = host_fixups(ctx, d_scal + 2, nhost, false, ctx->i_fix.p, 5, ctx->U.as<uint8_t>(), ctx->ulen,
+                        "VCF INFO decode pass", "its Float texts for the host differ from the check pass's count",
+                        nullptr, [&](const int64_t* w, const char* text, FixValue* V) {  // key, variant, element
+                          const int64_t q = w[0], k = w[1], j = w[2];
+                          if (q < 0 || q >= K || type[(size_t)q] != dqi::INFO_FLOAT || k < 0 || k >= n || j < 0 ||
+                              j >= width[(size_t)q])
+                            return false;
+                          V->dst = ctx->i_fval.as<double>() + base[(size_t)q] + k * width[(size_t)q] + j;
+                          V->bytes = 8;
+                          V->v.d = strtod(text, nullptr);
+                          return true;
+                        })))
+    return rc;
   ctx->info_type = type;
   ctx->info_width = width;
   ctx->info_base = base;

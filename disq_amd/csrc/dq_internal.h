@@ -80,6 +80,10 @@ __device__ unsigned int g_dq_chk[3];
   uint64_t dq_chk_take_##name() { return 0; }
 #endif
 
+// the name table the SAM and VCF kernels take (dqt::NameTable); a unit that wants the lookup's
+// bound counted defines DQT_CHECK before it includes this header
+#include "dq_text_core.h"
+
 // ------------------------------------------------------------------ hashing
 __host__ __device__ inline uint64_t dq_mix64(uint64_t z) {
   z ^= z >> 30;
@@ -398,13 +402,6 @@ void launch_span_hash(const uint8_t* base, const int64_t* start, const int32_t* 
                       uint64_t* hash, hipStream_t s);
 
 // ------------------------------------------------------------------ SAM text path (dq_sam.hip)
-struct SamRefs {           // the @SQ names: hashes sorted ascending (ties by index), see dq_sam_core.h
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* name_off;  // n + 1 offsets into names, by reference index
-  const uint8_t* names;
-  int32_t n;
-};
 // Lines of T[0, flen) from its terminator ends: value start and length (terminator excluded, a BOM
 // stripped from line 0 when bom), raw start, keep = the value does not start with '@'.
 void launch_sam_lines(const uint8_t* T, int64_t flen, const int64_t* term, int64_t nterm, int64_t nl,
@@ -417,23 +414,16 @@ void launch_sam_parts(const int64_t* splits, int64_t nsplit, const int64_t* lsta
 // Size pass over the n kept lines (kept[j] = line index): status[j], size[j] = 4 + block_size;
 // scal[0] (all ones) takes the smallest failing j, scal[1] (zero) the undecided floats.
 void launch_sam_sizes(const uint8_t* T, const int64_t* vstart, const int32_t* vlen, int64_t nl,
-                      const int64_t* kept, int64_t n, SamRefs refs, int32_t* status, int32_t* size,
+                      const int64_t* kept, int64_t n, dqt::NameTable refs, int32_t* status, int32_t* size,
                       unsigned long long* scal, hipStream_t s);
 // Encode pass: record j at rec[roff[j]], roff[n] = total bytes; SoA rows; undecided floats appended
 // to fix (3 words each: byte offset in rec, text offset in T, text length), counted in fix_cnt.
 void launch_sam_encode(const uint8_t* T, const int64_t* lstart, const int64_t* vstart,
-                       const int32_t* vlen, int64_t nl, const int64_t* kept, int64_t n, SamRefs refs,
+                       const int32_t* vlen, int64_t nl, const int64_t* kept, int64_t n, dqt::NameTable refs,
                        const int64_t* roff, const int32_t* size, uint8_t* rec, RecSoA soa,
                        int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt, hipStream_t s);
 
 // ------------------------------------------------------------------ VCF site decode (dq_vcf.hip)
-struct VcfContigs {        // the ##contig IDs: hashes sorted ascending (ties by index), see dq_vcf_core.h
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* name_off;  // n + 1 offsets into names, by contig index
-  const uint8_t* names;
-  int32_t n;
-};
 struct VcfCols {           // the columns of dq_variant_batch, one row per variant
   int32_t* contig;
   int32_t* pos;
@@ -451,13 +441,13 @@ struct VcfCols {           // the columns of dq_variant_batch, one row per varia
 // line's index in the file's line table); '#' lines are skipped.  scal[0] (all ones) takes the
 // smallest (line index << 8 | error class), scal[1] (zero) the undecided QUAL texts.
 void launch_vcf_validate(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
-                         const int64_t* lidx, int64_t n, int32_t G, VcfContigs ctg,
+                         const int64_t* lidx, int64_t n, int32_t G, dqt::NameTable ctg,
                          unsigned long long* scal, hipStream_t s);
 // Decode pass over the n kept lines (kept[j] = entry of the list of `total` lines): the columns;
 // undecided QUAL texts appended to fix (3 words each: variant, text offset in U, text length),
 // counted in fix_cnt.
 void launch_vcf_decode(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
-                       int64_t total, const int64_t* kept, int64_t n, int32_t G, VcfContigs ctg,
+                       int64_t total, const int64_t* kept, int64_t n, int32_t G, dqt::NameTable ctg,
                        VcfCols out, int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt,
                        hipStream_t s);
 // out[out_off[j] ...] = U[start[j], start[j] + len[j]) for the n variants (out_off[n] = total bytes)
@@ -465,7 +455,7 @@ void launch_vcf_gather(const uint8_t* U, int64_t ulen, const int64_t* start, con
                        const int64_t* out_off, int64_t n, uint8_t* out, hipStream_t s);
 
 // ------------------------------------------------------------------ VCF genotype decode (dq_vcf_gt.hip)
-struct GtIn {              // the kept variants of a text run, and what the site decode knows of them
+struct VcfLines {          // the kept variants of a text run, and where the site decode left their columns
   const uint8_t* U;
   int64_t ulen;
   const int64_t* vstart;   // value start / length of the `total` lines of the list
@@ -474,7 +464,10 @@ struct GtIn {              // the kept variants of a text run, and what the site
   int64_t total;
   const int64_t* kept;     // variant j = entry kept[j] of the list
   int64_t n;
-  const int32_t* col_end;  // VcfCols of the same variants: FORMAT starts at col_end[8 j + 7] + 1
+  const int32_t* col_end;  // VcfCols of the same variants: column c of variant j ends at col_end[8 j + c]
+};
+struct GtIn {              // FORMAT starts at col_end[8 j + 7] + 1
+  VcfLines ln;
   const int32_t* n_alt;
   const int32_t* n_sample_cols;
   int32_t S;               // the header's sample count, > 0
@@ -496,26 +489,11 @@ void launch_gt_decode(GtIn in, GtCols out, int32_t P, int64_t* fix, int64_t fix_
                       unsigned long long* scal, hipStream_t s);
 
 // ------------------------------------------------------------------ VCF INFO decode (dq_vcf_info.hip)
-struct InfoKeysDev {       // dqi::InfoKeys in device memory (dq_vcf_info_core.h), n <= 64
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* id_off;
-  const uint8_t* ids;
-  const uint8_t* type;
-  const uint8_t* hflag;
-  int32_t n;
-};
-struct InfoIn {            // the kept variants of a text run and their column ends, as GtIn
-  const uint8_t* U;
-  int64_t ulen;
-  const int64_t* vstart;
-  const int32_t* vlen;
-  const int64_t* lidx;
-  int64_t total;
-  const int64_t* kept;
-  int64_t n;
-  const int32_t* col_end;  // INFO is [col_end[8 j + 6] + 1, col_end[8 j + 7]) of variant j's value
-  InfoKeysDev keys;
+struct InfoIn {            // INFO is [col_end[8 j + 6] + 1, col_end[8 j + 7]) of variant j's value
+  VcfLines ln;
+  dqt::NameTable keys;     // dqi::InfoKeys in device memory (dq_vcf_info_core.h), n <= 64
+  const uint8_t* key_type;
+  const uint8_t* key_hflag;
 };
 struct InfoCols {          // the arrays of dq_info_batch, key-major: cell (q, k) at q * n + k
   uint8_t* flags;

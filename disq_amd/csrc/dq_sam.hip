@@ -16,23 +16,20 @@
 // voffset is the offset of the line's first byte in the file: SAM text has no virtual offsets.
 // Out of scope: interval traversal, LENIENT / SILENT tolerance of malformed lines, sharded and
 // multi-GPU SAM.  (SAM output is dq_samw.hip.)
-#include "dq_internal.h"
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DQS_CHECK(cond) DQ_CHK(cond, CHK_SAM)
+#define DQT_CHECK(cond) DQ_CHK(cond, CHK_SAM)
 #else
 #define DQS_CHECK(cond) ((void)0)
+#define DQT_CHECK(cond) ((void)0)
 #endif
+#include "dq_internal.h"
 #include "dq_sam_core.h"
 
 namespace dq {
 namespace {
 
 constexpr int32_t SAM_LONG = 2048;  // longer lines get a wave (the text path's TV_LONG)
-
-__device__ inline dqs::RefTable ref_table(const SamRefs& r) {
-  return dqs::RefTable{r.hash, r.idx, r.name_off, r.names, r.n};
-}
 
 __global__ __launch_bounds__(256) void sam_lines_kernel(const uint8_t* __restrict__ T, int64_t flen,
                                                         const int64_t* __restrict__ term,
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(const uint8_t* __restrict
                                                        const int64_t* __restrict__ vstart,
                                                        const int32_t* __restrict__ vlen, int64_t nl,
                                                        const int64_t* __restrict__ kept, int64_t n,
-                                                       SamRefs refs, int32_t* __restrict__ status,
+                                                       dqt::NameTable refs, int32_t* __restrict__ status,
                                                        int32_t* __restrict__ size,
                                                        unsigned long long* __restrict__ scal) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,7 +97,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(const uint8_t* __restrict
   const int32_t len = vlen[k];
   if (len > SAM_LONG) return;  // sam_size_long_kernel
   dqs::SamLineInfo I;
-  const int32_t st = dqs::sam_line_size(T + vstart[k], len, ref_table(refs), &I);
+  const int32_t st = dqs::sam_line_size(T + vstart[k], len, refs, &I);
   status[j] = st;
   size[j] = st ? 0 : I.size;
   if (st) atomicMin(&scal[0], (unsigned long long)j);
@@ -132,7 +129,7 @@ __global__ __launch_bounds__(256) void sam_size_long_kernel(const uint8_t* __res
                                                             const int32_t* __restrict__ vlen,
                                                             int64_t nl,
                                                             const int64_t* __restrict__ kept,
-                                                            int64_t n, SamRefs refs,
+                                                            int64_t n, dqt::NameTable refs,
                                                             int32_t* __restrict__ status,
                                                             int32_t* __restrict__ size,
                                                             unsigned long long* __restrict__ scal) {
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(256) void sam_size_long_kernel(const uint8_t* __res
     const dqs::SamTabs tb = wave_tabs(L, len, lane);
     if (lane == 0) {
       dqs::SamLineInfo I;
-      st = dqs::sam_line_walk(L, len, ref_table(refs), nullptr, 0, &I, nullptr, false, &tb);
+      st = dqs::sam_line_walk(L, len, refs, nullptr, 0, &I, nullptr, false, &tb);
       sz = I.size;
       nund = I.n_undecided;
       seq_off = I.seq_off;
@@ -207,7 +204,7 @@ __device__ inline void store_row(const RecSoA& soa, int64_t j, int64_t line_off,
 __global__ __launch_bounds__(256) void sam_encode_kernel(
     const uint8_t* __restrict__ T, const int64_t* __restrict__ lstart,
     const int64_t* __restrict__ vstart, const int32_t* __restrict__ vlen, int64_t nl,
-    const int64_t* __restrict__ kept, int64_t n, SamRefs refs, const int64_t* __restrict__ roff,
+    const int64_t* __restrict__ kept, int64_t n, dqt::NameTable refs, const int64_t* __restrict__ roff,
     const int32_t* __restrict__ size, uint8_t* __restrict__ rec, RecSoA soa, int64_t* __restrict__ fix,
     int64_t fix_cap, unsigned long long* __restrict__ fix_cnt) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -222,7 +219,7 @@ __global__ __launch_bounds__(256) void sam_encode_kernel(
   if (o < 0 || sz < 36 || o + sz > total) return;  // never store outside the record buffer
   const dqs::SamFixSink fx{fix, fix_cnt, fix_cap, o, vstart[k]};
   dqs::SamLineInfo I;
-  const int32_t st = dqs::sam_line_encode(T + vstart[k], len, ref_table(refs), rec + o, sz, &I, &fx);
+  const int32_t st = dqs::sam_line_encode(T + vstart[k], len, refs, rec + o, sz, &I, &fx);
   DQ_CHK(st == 0 && I.size == sz, CHK_SAM);
   (void)st;
   store_row(soa, j, lstart[k], I);
@@ -231,7 +228,7 @@ __global__ __launch_bounds__(256) void sam_encode_kernel(
 __global__ __launch_bounds__(256) void sam_encode_long_kernel(
     const uint8_t* __restrict__ T, const int64_t* __restrict__ lstart,
     const int64_t* __restrict__ vstart, const int32_t* __restrict__ vlen, int64_t nl,
-    const int64_t* __restrict__ kept, int64_t n, SamRefs refs, const int64_t* __restrict__ roff,
+    const int64_t* __restrict__ kept, int64_t n, dqt::NameTable refs, const int64_t* __restrict__ roff,
     const int32_t* __restrict__ size, uint8_t* __restrict__ rec, RecSoA soa, int64_t* __restrict__ fix,
     int64_t fix_cap, unsigned long long* __restrict__ fix_cnt) {
   const int lane = threadIdx.x & 63;
@@ -251,7 +248,7 @@ __global__ __launch_bounds__(256) void sam_encode_long_kernel(
     if (lane == 0) {
       const dqs::SamFixSink fx{fix, fix_cnt, fix_cap, o, vstart[k]};
       dqs::SamLineInfo I;
-      const int32_t st = dqs::sam_line_walk(L, len, ref_table(refs), rec + o, sz, &I, &fx, false, &tb);
+      const int32_t st = dqs::sam_line_walk(L, len, refs, rec + o, sz, &I, &fx, false, &tb);
       DQ_CHK(st == 0 && I.size == sz, CHK_SAM);
       (void)st;
       store_row(soa, j, lstart[k], I);
@@ -319,7 +316,7 @@ static unsigned wave_grid(int64_t n) {  // 4 waves per block, grid-stride past 2
 }
 
 void launch_sam_sizes(const uint8_t* T, const int64_t* vstart, const int32_t* vlen, int64_t nl,
-                      const int64_t* kept, int64_t n, SamRefs refs, int32_t* status, int32_t* size,
+                      const int64_t* kept, int64_t n, dqt::NameTable refs, int32_t* status, int32_t* size,
                       unsigned long long* scal, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(sam_size_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, T, vstart,
@@ -329,7 +326,7 @@ void launch_sam_sizes(const uint8_t* T, const int64_t* vstart, const int32_t* vl
 }
 
 void launch_sam_encode(const uint8_t* T, const int64_t* lstart, const int64_t* vstart,
-                       const int32_t* vlen, int64_t nl, const int64_t* kept, int64_t n, SamRefs refs,
+                       const int32_t* vlen, int64_t nl, const int64_t* kept, int64_t n, dqt::NameTable refs,
                        const int64_t* roff, const int32_t* size, uint8_t* rec, RecSoA soa,
                        int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt, hipStream_t s) {
   if (n <= 0) return;

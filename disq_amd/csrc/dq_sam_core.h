@@ -2,34 +2,26 @@
 // into one BAM record as htsjdk SAMLineParser.parseLine + BAMRecordCodec.encode + BinaryTagCodec
 // do it, restated by tests/samutil.py (sam_line_to_bam_record), whose order of checks this keeps so
 // that the first error of a line is the same one.  The kernels of dq_sam.hip and the host program
-// tools/sam_core_check.cpp compile the same functions (the __HIPCC__ guards, as in
-// dq_inflate_core.h).
+// tools/sam_core_check.cpp compile the same functions.  The @SQ names are a dqt::NameTable, the
+// integer columns dqt::parse_dec (dq_text_core.h, which also holds the __HIPCC__ guards).
 //
 // One walk serves both passes: with out == nullptr it validates and sizes the record, with out set
 // it writes the bytes; so the size a record was given and the bytes it gets cannot disagree.
 #pragma once
 #include <stdint.h>
 
-#include <algorithm>
-#include <string>
-#include <utility>
-#include <vector>
-
 #include "dq_sam_pow5.h"
+#include "dq_text_core.h"
 
-#ifndef __HIPCC__
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#endif
-
-#define DQS_INLINE __host__ __device__ inline
 #ifndef DQS_CHECK  // dq_sam.hip counts a failed bound here in the bounds-checked build
 #define DQS_CHECK(cond) ((void)0)
 #endif
 
 namespace dqs {
+
+using dqt::is_digit;
+using dqt::NameTable;  // the @SQ names, by reference index
+using dqt::parse_dec;
 
 // Line status: 0, a column (the spelling of samutil.SamError.what is sam_status_name's), or
 // SAM_E_TAG | (bytes of the tag name present, 0..2) << 16 | name[0] << 8 | name[1].
@@ -66,71 +58,13 @@ inline const char* sam_status_name(int32_t st, char* buf) {
   return buf;
 }
 
-DQS_INLINE int32_t sam_tag_error(const uint8_t* f, int32_t n) {
+DQT_INLINE int32_t sam_tag_error(const uint8_t* f, int32_t n) {
   const int32_t k = n < 2 ? n : 2;
   return SAM_E_TAG | (k << 16) | ((k > 0 ? (int32_t)f[0] : 0) << 8) | (k > 1 ? (int32_t)f[1] : 0);
 }
 
-// ------------------------------------------------------------------ @SQ names
-// hash: FNV-1a of every name, sorted ascending, ties by reference index (so equal names resolve
-// to the first, as list.index does); idx: the reference index of each sorted entry; the name
-// bytes of reference r are names[name_off[r], name_off[r + 1]).  Built on the host.
-struct RefTable {
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* name_off;
-  const uint8_t* names;
-  int32_t n;
-};
-
-DQS_INLINE uint64_t sam_name_hash(const uint8_t* p, int32_t n) {
-  uint64_t h = 0xcbf29ce484222325ULL;
-  for (int32_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ULL;
-  return h;
-}
-
-DQS_INLINE int32_t sam_ref_lookup(const RefTable& R, const uint8_t* p, int32_t n) {
-  const uint64_t h = sam_name_hash(p, n);
-  int32_t lo = 0, hi = R.n;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (R.hash[mid] < h) lo = mid + 1;
-    else hi = mid;
-  }
-  for (; lo < R.n && R.hash[lo] == h; lo++) {
-    const int32_t r = R.idx[lo];
-    const int32_t a = R.name_off[r];
-    if (R.name_off[r + 1] - a != n) continue;
-    bool eq = true;
-    for (int32_t i = 0; i < n && eq; i++) eq = R.names[a + i] == p[i];
-    if (eq) return r;
-  }
-  return -1;
-}
-
 // ------------------------------------------------------------------ numbers
-DQS_INLINE bool sam_digit(uint8_t c) { return c >= '0' && c <= '9'; }
-
-// [-+]?[0-9]+ (the sign only when sgn) within [lo, hi]; any number of digits.
-DQS_INLINE bool sam_dec(const uint8_t* t, int32_t n, bool sgn, int64_t lo, int64_t hi, int64_t* v) {
-  int32_t i = 0;
-  bool neg = false;
-  if (sgn && n > 0 && (t[0] == '-' || t[0] == '+')) {
-    neg = t[0] == '-';
-    i = 1;
-  }
-  if (i >= n) return false;
-  int64_t x = 0;
-  for (; i < n; i++) {
-    if (!sam_digit(t[i])) return false;
-    if (x < (1ll << 40)) x = x * 10 + (t[i] - '0');  // saturates far above every range
-  }
-  if (neg) x = -x;
-  *v = x;
-  return x >= lo && x <= hi;
-}
-
-DQS_INLINE void sam_mul64(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
+DQT_INLINE void sam_mul64(uint64_t a, uint64_t b, uint64_t* hi, uint64_t* lo) {
 #if defined(__HIP_DEVICE_COMPILE__)
   *lo = a * b;
   *hi = __umul64hi(a, b);
@@ -150,7 +84,7 @@ enum : int { SAM_F_OK = 0, SAM_F_UNDECIDED = 1, SAM_F_BAD = 2 };
 // of five, refined by the low half when the first product leaves the rounding open.
 // SAM_F_UNDECIDED (bits = 0): non-zero digits past the 19th, or a product that cannot tell which
 // side of a rounding boundary the value lies on; the caller converts those texts with strtof.
-DQS_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
+DQT_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
   static constexpr uint64_t POW5[DQ_SAM_POW5_QMAX - DQ_SAM_POW5_QMIN + 1][2] = {DQ_SAM_POW5_TABLE};
   *bits = 0;
   int32_t i = 0;
@@ -161,7 +95,7 @@ DQS_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
   int64_t q = 0;       // value = w * 10^q (+ the dropped digits)
   bool dropped = false;
   int32_t ni = 0, nf = 0;
-  for (; i < n && sam_digit(t[i]); i++, ni++) {
+  for (; i < n && is_digit(t[i]); i++, ni++) {
     const uint32_t d = t[i] - '0';
     if (nd == 0 && d == 0) continue;  // leading zeros
     if (nd < 19) {
@@ -174,7 +108,7 @@ DQS_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
   }
   const bool dot = i < n && t[i] == '.';
   if (dot) {
-    for (i++; i < n && sam_digit(t[i]); i++, nf++) {
+    for (i++; i < n && is_digit(t[i]); i++, nf++) {
       const uint32_t d = t[i] - '0';
       if (nd < 19) {
         w = w * 10 + d;
@@ -192,7 +126,7 @@ DQS_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
     if (i < n && (t[i] == '-' || t[i] == '+')) eneg = t[i++] == '-';
     int64_t x = 0;
     int32_t nx = 0;
-    for (; i < n && sam_digit(t[i]); i++, nx++)
+    for (; i < n && is_digit(t[i]); i++, nx++)
       if (x < 1000000) x = x * 10 + (t[i] - '0');
     if (nx == 0) return SAM_F_BAD;
     q += eneg ? -x : x;
@@ -259,7 +193,7 @@ DQS_INLINE int sam_parse_float(const uint8_t* t, int32_t n, uint32_t* bits) {
 }
 
 // ------------------------------------------------------------------ the line walk
-DQS_INLINE int sam_seq_code(uint8_t c) {  // =ACMGRSVTWYHKDBN in either case, '.' as N; else -1
+DQT_INLINE int sam_seq_code(uint8_t c) {  // =ACMGRSVTWYHKDBN in either case, '.' as N; else -1
   if (c == '.') return 15;
   if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
   switch (c) {
@@ -283,7 +217,7 @@ DQS_INLINE int sam_seq_code(uint8_t c) {  // =ACMGRSVTWYHKDBN in either case, '.
   }
 }
 
-DQS_INLINE int sam_cigar_code(uint8_t c) {  // MIDNSHP=X
+DQT_INLINE int sam_cigar_code(uint8_t c) {  // MIDNSHP=X
   switch (c) {
     case 'M': return 0;
     case 'I': return 1;
@@ -298,7 +232,7 @@ DQS_INLINE int sam_cigar_code(uint8_t c) {  // MIDNSHP=X
   }
 }
 
-DQS_INLINE int32_t sam_reg2bin(int32_t beg, int32_t end) {
+DQT_INLINE int32_t sam_reg2bin(int32_t beg, int32_t end) {
   end -= 1;
   if (beg >> 14 == end >> 14) return 4681 + (beg >> 14);
   if (beg >> 17 == end >> 17) return 585 + (beg >> 17);
@@ -331,30 +265,30 @@ struct SamOut {  // a counting or writing byte sink; nothing is stored at or pas
   uint8_t* p;
   int32_t o;
   int32_t lim;
-  DQS_INLINE void put8(uint32_t v) {
+  DQT_INLINE void put8(uint32_t v) {
     if (p) {
       DQS_CHECK(o < lim);
       if (o < lim) p[o] = (uint8_t)v;
     }
     o++;
   }
-  DQS_INLINE void put16(uint32_t v) {
+  DQT_INLINE void put16(uint32_t v) {
     put8(v);
     put8(v >> 8);
   }
-  DQS_INLINE void put32(uint32_t v) {
+  DQT_INLINE void put32(uint32_t v) {
     put16(v);
     put16(v >> 16);
   }
   // whole little-endian words: one store each (the alignment is the record's, arbitrary)
-  DQS_INLINE void put_w32(uint32_t v) {
+  DQT_INLINE void put_w32(uint32_t v) {
     if (p) {
       DQS_CHECK(o + 4 <= lim);
       if (o + 4 <= lim) __builtin_memcpy(p + o, &v, 4);
     }
     o += 4;
   }
-  DQS_INLINE void put_w64(uint64_t v) {
+  DQT_INLINE void put_w64(uint64_t v) {
     if (p) {
       DQS_CHECK(o + 8 <= lim);
       if (o + 8 <= lim) __builtin_memcpy(p + o, &v, 8);
@@ -365,7 +299,7 @@ struct SamOut {  // a counting or writing byte sink; nothing is stored at or pas
 
 // Eight bases at src (one 8-byte load) -> their four packed bytes as a little-endian word; false
 // when one of them is no base.
-DQS_INLINE bool sam_pack8(const uint8_t* src, uint32_t* pk) {
+DQT_INLINE bool sam_pack8(const uint8_t* src, uint32_t* pk) {
   uint64_t w;
   __builtin_memcpy(&w, src, 8);
   uint32_t v = 0;
@@ -381,7 +315,7 @@ DQS_INLINE bool sam_pack8(const uint8_t* src, uint32_t* pk) {
 }
 
 // Eight quality bytes at src minus 33 each; false when one of them is below 33.
-DQS_INLINE bool sam_qual8(const uint8_t* src, uint64_t* out) {
+DQT_INLINE bool sam_qual8(const uint8_t* src, uint64_t* out) {
   uint64_t w;
   __builtin_memcpy(&w, src, 8);
   uint64_t v = 0;
@@ -396,7 +330,7 @@ DQS_INLINE bool sam_qual8(const uint8_t* src, uint64_t* out) {
   return ok;
 }
 
-DQS_INLINE void sam_poke32(uint8_t* p, int32_t o, uint32_t v) {
+DQT_INLINE void sam_poke32(uint8_t* p, int32_t o, uint32_t v) {
   p[o] = (uint8_t)v;
   p[o + 1] = (uint8_t)(v >> 8);
   p[o + 2] = (uint8_t)(v >> 16);
@@ -404,7 +338,7 @@ DQS_INLINE void sam_poke32(uint8_t* p, int32_t o, uint32_t v) {
 }
 
 // One float value of a tag: validated, sized, written (a zero and a fix-up entry when undecided).
-DQS_INLINE bool sam_put_float(const uint8_t* L, int32_t a, int32_t n, SamOut& O, SamLineInfo* I,
+DQT_INLINE bool sam_put_float(const uint8_t* L, int32_t a, int32_t n, SamOut& O, SamLineInfo* I,
                               const SamFixSink* fx) {
   uint32_t bits;
   const int r = sam_parse_float(L + a, n, &bits);
@@ -442,7 +376,7 @@ struct SamTabs {
   int32_t n;
 };
 
-DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& R, uint8_t* out,
+DQT_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const NameTable& R, uint8_t* out,
                                  int32_t out_cap, SamLineInfo* I, const SamFixSink* fx, bool bulk,
                                  const SamTabs* tabs = nullptr) {
   *I = SamLineInfo{};
@@ -468,27 +402,27 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
   const int32_t lname = fe[0] - fs[0];
   if (lname < 1 || lname > 254) return SAM_E_QNAME;
   int64_t v;
-  if (!sam_dec(L + fs[1], fe[1] - fs[1], false, 0, 65535, &v)) return SAM_E_FLAG;
+  if (!parse_dec(L + fs[1], fe[1] - fs[1], false, 0, 65535, &v)) return SAM_E_FLAG;
   const int32_t flag = (int32_t)v;
   int32_t ref = -1;
   if (!(fe[2] - fs[2] == 1 && L[fs[2]] == '*')) {
-    ref = sam_ref_lookup(R, L + fs[2], fe[2] - fs[2]);
+    ref = dqt::name_lookup(R, L + fs[2], fe[2] - fs[2]);
     if (ref < 0) return SAM_E_RNAME;
   }
-  if (!sam_dec(L + fs[3], fe[3] - fs[3], false, 0, 2147483647ll, &v)) return SAM_E_POS;
+  if (!parse_dec(L + fs[3], fe[3] - fs[3], false, 0, 2147483647ll, &v)) return SAM_E_POS;
   const int32_t beg = (int32_t)(v - 1);
-  if (!sam_dec(L + fs[4], fe[4] - fs[4], false, 0, 255, &v)) return SAM_E_MAPQ;
+  if (!parse_dec(L + fs[4], fe[4] - fs[4], false, 0, 255, &v)) return SAM_E_MAPQ;
   const int32_t mapq = (int32_t)v;
   int32_t nref = -1;
   if (fe[6] - fs[6] == 1 && L[fs[6]] == '=') {
     nref = ref;
   } else if (!(fe[6] - fs[6] == 1 && L[fs[6]] == '*')) {
-    nref = sam_ref_lookup(R, L + fs[6], fe[6] - fs[6]);
+    nref = dqt::name_lookup(R, L + fs[6], fe[6] - fs[6]);
     if (nref < 0) return SAM_E_RNEXT;
   }
-  if (!sam_dec(L + fs[7], fe[7] - fs[7], false, 0, 2147483647ll, &v)) return SAM_E_PNEXT;
+  if (!parse_dec(L + fs[7], fe[7] - fs[7], false, 0, 2147483647ll, &v)) return SAM_E_PNEXT;
   const int32_t npos = (int32_t)(v - 1);
-  if (!sam_dec(L + fs[8], fe[8] - fs[8], true, -2147483648ll, 2147483647ll, &v)) return SAM_E_TLEN;
+  if (!parse_dec(L + fs[8], fe[8] - fs[8], true, -2147483648ll, 2147483647ll, &v)) return SAM_E_TLEN;
   const int32_t tlen = (int32_t)v;
   const bool seq_star = fe[9] - fs[9] == 1 && L[fs[9]] == '*';
   const bool qual_star = fe[10] - fs[10] == 1 && L[fs[10]] == '*';
@@ -507,7 +441,7 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
     while (x < fe[5]) {
       int64_t n = 0;
       int32_t nd = 0;
-      for (; x < fe[5] && sam_digit(L[x]); x++, nd++)
+      for (; x < fe[5] && is_digit(L[x]); x++, nd++)
         if (nd < 11) n = n * 10 + (L[x] - '0');
       if (nd == 0 || x >= fe[5]) return SAM_E_CIGAR;
       const int k = sam_cigar_code(L[x++]);
@@ -574,7 +508,7 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
       O.put8('A');
       O.put8(val[0]);
     } else if (ty == 'i') {
-      if (!sam_dec(val, vn, true, -2147483648ll, 4294967295ll, &v)) return bad;
+      if (!parse_dec(val, vn, true, -2147483648ll, 4294967295ll, &v)) return bad;
       if (v > 2147483647ll) {
         O.put8('I');
         O.put32((uint32_t)v);
@@ -609,7 +543,7 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
       O.put8('H');
       for (int32_t i = 0; i < vn; i++) {
         const uint8_t c = val[i];
-        if (!(sam_digit(c) || (c >= 'A' && c <= 'F'))) return bad;
+        if (!(is_digit(c) || (c >= 'A' && c <= 'F'))) return bad;
         O.put8(c);
       }
       O.put8(0);
@@ -644,7 +578,7 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
         if (sub == 'f') {
           if (!sam_put_float(L, va + ia, x - ia, O, I, fx)) return bad;
         } else {
-          if (!sam_dec(val + ia, x - ia, true, lo, hi, &v)) return bad;
+          if (!parse_dec(val + ia, x - ia, true, lo, hi, &v)) return bad;
           if (w == 1) O.put8((uint32_t)v);
           else if (w == 2) O.put16((uint32_t)v);
           else O.put32((uint32_t)v);
@@ -693,17 +627,17 @@ DQS_INLINE int32_t sam_line_walk(const uint8_t* L, int32_t len, const RefTable& 
 }
 
 // Size pass: validates every column and tag; I->size = the record's bytes (4 + block_size).
-DQS_INLINE int32_t sam_line_size(const uint8_t* line, int32_t len, const RefTable& R, SamLineInfo* I) {
+DQT_INLINE int32_t sam_line_size(const uint8_t* line, int32_t len, const NameTable& R, SamLineInfo* I) {
   return sam_line_walk(line, len, R, nullptr, 0, I, nullptr, true);
 }
 
 // Encode pass over a line the size pass accepted: writes the I->size bytes at out.
-DQS_INLINE int32_t sam_line_encode(const uint8_t* line, int32_t len, const RefTable& R, uint8_t* out,
+DQT_INLINE int32_t sam_line_encode(const uint8_t* line, int32_t len, const NameTable& R, uint8_t* out,
                                    int32_t out_cap, SamLineInfo* I, const SamFixSink* fx) {
   return sam_line_walk(line, len, R, out, out_cap, I, fx, true);
 }
 
-// ------------------------------------------------------------------ host: header and name table
+// ------------------------------------------------------------------ host: the header
 // The leading '@' lines of a SAM text as a BAM header (samutil.sam_header_to_bam): BAM\1, l_text,
 // every such line followed by LF, n_ref, then per @SQ line l_name, name, NUL, LN.  `whole`: t is the
 // whole file (else a prefix: returns 1 when the header may run past it).  -1: a bad @SQ line.
@@ -750,7 +684,7 @@ inline int sam_header_build(const uint8_t* t, int64_t n, bool whole, SamHeader* 
       }
       int64_t v = 0;
       if (!has_sn || !has_ln ||
-          !sam_dec((const uint8_t*)ln.data(), (int32_t)ln.size(), true, -2147483648ll, 2147483647ll, &v))
+          !parse_dec((const uint8_t*)ln.data(), (int32_t)ln.size(), true, -2147483648ll, 2147483647ll, &v))
         return -1;
       H->names.push_back(sn);
       H->lens.push_back((int32_t)v);
@@ -772,35 +706,6 @@ inline int sam_header_build(const uint8_t* t, int64_t n, bool whole, SamHeader* 
     put32((uint32_t)H->lens[r]);
   }
   return 0;
-}
-
-struct RefTableHost {
-  std::vector<uint64_t> hash;
-  std::vector<int32_t> idx, name_off;
-  std::vector<uint8_t> names;
-  RefTable view() const {
-    return RefTable{hash.data(), idx.data(), name_off.data(), names.data(), (int32_t)idx.size()};
-  }
-};
-
-inline void sam_ref_table_build(const std::vector<std::string>& names, RefTableHost* T) {
-  const size_t n = names.size();
-  T->name_off.assign(1, 0);
-  T->names.clear();
-  std::vector<std::pair<uint64_t, int32_t>> key;
-  for (size_t r = 0; r < n; r++) {
-    T->names.insert(T->names.end(), names[r].begin(), names[r].end());
-    T->name_off.push_back((int32_t)T->names.size());
-    key.push_back({sam_name_hash((const uint8_t*)names[r].data(), (int32_t)names[r].size()), (int32_t)r});
-  }
-  std::sort(key.begin(), key.end());
-  T->hash.resize(n);
-  T->idx.resize(n);
-  for (size_t i = 0; i < n; i++) {
-    T->hash[i] = key[i].first;
-    T->idx[i] = key[i].second;
-  }
-  T->names.push_back(0);  // never empty
 }
 
 }  // namespace dqs

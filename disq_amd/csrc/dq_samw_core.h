@@ -3,7 +3,7 @@
 // String.trim does and followed by LF (SamSink.save), restated by tests/samwriteutil.py
 // (record_to_sam_line), whose order of checks this keeps so that the first error of a record is the
 // same one.  The kernels of dq_samw.hip and the host program tools/sam_write_check.cpp compile the
-// same functions (the __HIPCC__ guards of dq_sam_core.h).
+// same functions (the __HIPCC__ guards of dq_text_core.h).
 //
 // One walk serves both passes: with out == nullptr it validates and sizes the line, with out set it
 // writes the bytes, every store bounded by the size the first pass gave; so a line can never get
@@ -38,7 +38,7 @@ struct Sink {
   bool over = false;  // a byte that belongs to the line did not fit
 };
 
-DQS_INLINE void put(Sink& s, uint8_t b) {
+DQT_INLINE void put(Sink& s, uint8_t b) {
   if (!s.started) {
     if (b <= 0x20) return;
     s.started = true;
@@ -51,19 +51,19 @@ DQS_INLINE void put(Sink& s, uint8_t b) {
   if (b > 0x20) s.keep = s.pos;
 }
 
-DQS_INLINE void put_bytes(Sink& s, const uint8_t* p, int64_t n) {
+DQT_INLINE void put_bytes(Sink& s, const uint8_t* p, int64_t n) {
   for (int64_t i = 0; i < n; i++) put(s, p[i]);
 }
 
 // Two digits of q < 100: the tens in the low byte.
-DQS_INLINE uint32_t dec2(uint32_t q) {
+DQT_INLINE uint32_t dec2(uint32_t q) {
   const uint32_t t = (q * 103u) >> 10;
   return t | ((q - 10u * t) << 8);
 }
 
 // The eight digits of x < 10^8 as ASCII, the first digit in the low byte (divisions by constants:
 // multiply and shift).
-DQS_INLINE uint64_t dec8(uint32_t x) {
+DQT_INLINE uint64_t dec8(uint32_t x) {
   const uint32_t hi = x / 10000u, lo = x - hi * 10000u;
   const uint32_t a = hi / 100u, b = hi - a * 100u, c = lo / 100u, d = lo - c * 100u;
   const uint64_t w = (uint64_t)dec2(a) | (uint64_t)dec2(b) << 16 | (uint64_t)dec2(c) << 32 |
@@ -71,12 +71,12 @@ DQS_INLINE uint64_t dec8(uint32_t x) {
   return w + 0x3030303030303030ull;
 }
 
-DQS_INLINE int dec_len(uint32_t v) {  // v < 10^9
+DQT_INLINE int dec_len(uint32_t v) {  // v < 10^9
   return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 :
          v < 1000000u ? 6 : v < 10000000u ? 7 : v < 100000000u ? 8 : 9;
 }
 
-DQS_INLINE void put_u32(Sink& s, uint32_t v) {
+DQT_INLINE void put_u32(Sink& s, uint32_t v) {
   uint32_t low = v;
   int n;
   if (v >= 100000000u) {
@@ -92,7 +92,7 @@ DQS_INLINE void put_u32(Sink& s, uint32_t v) {
   for (int i = 0; i < n; i++) put(s, (uint8_t)(w >> (8 * i)));
 }
 
-DQS_INLINE void put_i32(Sink& s, int32_t v) {
+DQT_INLINE void put_i32(Sink& s, int32_t v) {
   if (v < 0) {
     put(s, '-');
     put_u32(s, 0u - (uint32_t)v);
@@ -102,14 +102,14 @@ DQS_INLINE void put_i32(Sink& s, int32_t v) {
 }
 
 // ------------------------------------------------------------------ Float.toString
-DQS_INLINE uint32_t mul_shift32(uint32_t m, uint64_t factor, int32_t shift) {  // shift > 32
+DQT_INLINE uint32_t mul_shift32(uint32_t m, uint64_t factor, int32_t shift) {  // shift > 32
   const uint64_t b0 = (uint64_t)m * (uint32_t)factor, b1 = (uint64_t)m * (uint32_t)(factor >> 32);
   return (uint32_t)(((b0 >> 32) + b1) >> (shift - 32));
 }
-DQS_INLINE int32_t pow5bits(int32_t e) { return (int32_t)(((uint32_t)e * 1217359u) >> 19) + 1; }
-DQS_INLINE int32_t log10_pow2(int32_t e) { return (int32_t)(((uint32_t)e * 78913u) >> 18); }
-DQS_INLINE int32_t log10_pow5(int32_t e) { return (int32_t)(((uint32_t)e * 732923u) >> 20); }
-DQS_INLINE bool multiple_of_pow5(uint32_t v, int32_t p) {
+DQT_INLINE int32_t pow5bits(int32_t e) { return (int32_t)(((uint32_t)e * 1217359u) >> 19) + 1; }
+DQT_INLINE int32_t log10_pow2(int32_t e) { return (int32_t)(((uint32_t)e * 78913u) >> 18); }
+DQT_INLINE int32_t log10_pow5(int32_t e) { return (int32_t)(((uint32_t)e * 732923u) >> 20); }
+DQT_INLINE bool multiple_of_pow5(uint32_t v, int32_t p) {
   int32_t c = 0;
   while (v != 0 && v % 5u == 0) {
     v /= 5u;
@@ -123,7 +123,7 @@ DQS_INLINE bool multiple_of_pow5(uint32_t v, int32_t p) {
 // nearest, ties to even) those with the fewest digits, of these the nearest, on a tie the even one
 // (the Ryu scheme, Adams 2018: the value and both ends of its rounding interval, scaled by a power
 // of ten with one 32 x 64-bit product each, lose digits together while they still differ).
-DQS_INLINE void samw_shortest(uint32_t bits, uint32_t* digits, int32_t* e10) {
+DQT_INLINE void samw_shortest(uint32_t bits, uint32_t* digits, int32_t* e10) {
   static constexpr uint64_t INV[DQ_SAMW_POW5_INV_N] = {DQ_SAMW_POW5_INV_TABLE};
   static constexpr uint64_t POW[DQ_SAMW_POW5_N] = {DQ_SAMW_POW5_TABLE};
   const uint32_t frac = bits & 0x7fffffu, ex = (bits >> 23) & 0xffu;
@@ -247,7 +247,7 @@ DQS_INLINE void samw_shortest(uint32_t bits, uint32_t* digits, int32_t* e10) {
 }
 
 // Float.toString (the JDK 19+ contract) of the binary32 with these bits: at most 16 bytes.
-DQS_INLINE void put_float(Sink& s, uint32_t bits) {
+DQT_INLINE void put_float(Sink& s, uint32_t bits) {
   const uint32_t frac = bits & 0x7fffffu, ex = (bits >> 23) & 0xffu;
   if (ex == 0xffu && frac != 0) {
     put(s, 'N');
@@ -301,12 +301,12 @@ DQS_INLINE void put_float(Sink& s, uint32_t bits) {
 }
 
 // ------------------------------------------------------------------ one record
-DQS_INLINE int32_t rd32(const uint8_t* p) {
+DQT_INLINE int32_t rd32(const uint8_t* p) {
   uint32_t v;
   __builtin_memcpy(&v, p, 4);
   return (int32_t)v;
 }
-DQS_INLINE uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+DQT_INLINE uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 
 struct Layout {     // byte offsets from the block_size word
   int64_t end;      // 4 + block_size
@@ -315,7 +315,7 @@ struct Layout {     // byte offsets from the block_size word
 };
 
 // The fixed part and the parts it sizes must lie inside the record, the record inside `avail`.
-DQS_INLINE int32_t samw_layout(const uint8_t* r, int64_t avail, Layout* L) {
+DQT_INLINE int32_t samw_layout(const uint8_t* r, int64_t avail, Layout* L) {
   if (avail < 36) return dqs::SAM_E_FIELDS;
   const int32_t bs = rd32(r);
   if (bs < 32 || 4 + (int64_t)bs > avail) return dqs::SAM_E_FIELDS;
@@ -333,14 +333,14 @@ DQS_INLINE int32_t samw_layout(const uint8_t* r, int64_t avail, Layout* L) {
 }
 
 // Eight qualities: all 0xFF, or one above 93 (0xFF in a partly filled array included)?
-DQS_INLINE void samw_qual8(uint64_t w, bool* all_ff, bool* bad) {
+DQT_INLINE void samw_qual8(uint64_t w, bool* all_ff, bool* bad) {
   *all_ff = *all_ff && w == ~0ull;
   const uint64_t H = 0x8080808080808080ull;
   *bad = *bad || ((w | ((w & ~H) + 0x2222222222222222ull)) & H) != 0;  // 94 + 34 = 128
 }
 
 // Four packed bytes (the first in the low byte) into eight bases, the first in the low byte.
-DQS_INLINE uint64_t samw_seq8(uint32_t pk) {
+DQT_INLINE uint64_t samw_seq8(uint32_t pk) {
   const uint64_t T0 = 0x52474d43413dull | 0x5653ull << 48;  // "=ACMGRSV"
   const uint64_t T1 = 0x4e42444b48595754ull;                // "TWYHKDBN"
   uint64_t o = 0;
@@ -362,7 +362,7 @@ struct Walk {
 // written, only stepped over (a wave shares them; the caller has scanned QUAL and says whether it
 // prints as '*').  Returns the first failing check: fields, QNAME, RNAME, CIGAR, RNEXT, QUAL, then
 // the tags as stored.
-DQS_INLINE int32_t samw_record_walk(const uint8_t* r, int64_t avail, const RefNames& R, uint8_t* out,
+DQT_INLINE int32_t samw_record_walk(const uint8_t* r, int64_t avail, const RefNames& R, uint8_t* out,
                                     int64_t cap, bool bulk_skip, bool qual_star_in, Walk* W) {
   Layout& L = W->L;
   W->size = 0;

@@ -13,13 +13,14 @@
 //   gather     the first col_end[7] bytes of every variant (the SITES export), a wave per line.
 // Every load of a line lies in [value start, value start + len); the LDS staging copies whole
 // 16-byte words of a block's span of the stream, which end inside the zero bytes behind it.
-#include "dq_internal.h"
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DQV_CHECK(cond) DQ_CHK(cond, CHK_VCF)
+#define DQT_CHECK(cond) DQ_CHK(cond, CHK_VCF)
 #else
 #define DQV_CHECK(cond) ((void)0)
+#define DQT_CHECK(cond) ((void)0)
 #endif
+#include "dq_internal.h"
 #include "dq_vcf_core.h"
 #include "dq_vcf_stage.h"
 
@@ -27,10 +28,6 @@ namespace dq {
 namespace {
 
 constexpr int32_t VCF_LONG = 2048;  // longer lines get a wave (the text path's TV_LONG)
-
-__device__ inline dqv::ContigTable contig_table(const VcfContigs& c) {
-  return dqv::ContigTable{c.hash, c.idx, c.name_off, c.names, c.n};
-}
 
 // The first 8 TABs of a long line, found by the whole wave 64 bytes at a time (every lane ends with
 // the same list); with `count` the scan goes on to the line's end and counts every TAB.
@@ -81,22 +78,20 @@ __device__ inline bool data_line(const uint8_t* __restrict__ U, int64_t ulen, in
 __global__ __launch_bounds__(256) void vcf_validate_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ vstart,
     const int32_t* __restrict__ vlen, const int64_t* __restrict__ lidx, int64_t n, int32_t G,
-    VcfContigs ctg, unsigned long long* __restrict__ scal) {
+    dqt::NameTable ctg, unsigned long long* __restrict__ scal) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[VCF_STAGE];
   const int64_t t0 = (int64_t)blockIdx.x * 256, t = t0 + threadIdx.x;
-  const int64_t tl = t0 + 255 < n ? t0 + 255 : n - 1;  // t0 < n: the grid has no empty block
-  const StageSpan sp = stage_span(U, ulen, vstart[t0], vstart[tl] + vlen[tl], stage);
+  const StageSpan sp = stage_block(VcfLines{U, ulen, vstart, vlen, lidx, n, nullptr, n, nullptr}, t0, stage);
   if (t >= n) return;
   const int32_t len = vlen[t];
   if (len > VCF_LONG) return;  // vcf_validate_long_kernel
   const int64_t a = vstart[t];
   if (!data_line(U, ulen, a, len)) return;
   dqv::VcfSite S;
-  int32_t st;
-  if (sp.staged && a >= sp.lo && a + len <= sp.hi)
-    st = dqv::vcf_line_walk(stage + (a - sp.lo), len, G != 0, contig_table(ctg), nullptr, false, &S);
-  else
-    st = dqv::vcf_line_walk(U + a, len, G != 0, contig_table(ctg), nullptr, false, &S);
+  // two calls: the walk's loads are LDS loads in one and memory loads in the other, not flat ones
+  const int32_t st = in_stage(sp, a, len)
+                         ? dqv::vcf_line_walk(stage + (a - sp.lo), len, G != 0, ctg, nullptr, false, &S)
+                         : dqv::vcf_line_walk(U + a, len, G != 0, ctg, nullptr, false, &S);
   if (st) atomicMin(&scal[0], (unsigned long long)lidx[t] << 8 | (unsigned long long)st);
   else if (S.qual_undecided) atomicAdd(&scal[1], 1ull);
 }
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(256) void vcf_validate_kernel(
 __global__ __launch_bounds__(256) void vcf_validate_long_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ vstart,
     const int32_t* __restrict__ vlen, const int64_t* __restrict__ lidx, int64_t n, int32_t G,
-    VcfContigs ctg, unsigned long long* __restrict__ scal) {
+    dqt::NameTable ctg, unsigned long long* __restrict__ scal) {
   __shared__ uint8_t slots[4 * VCF_WSLOT];
   const int lane = threadIdx.x & 63;
   const int64_t nwave = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -118,9 +113,9 @@ __global__ __launch_bounds__(256) void vcf_validate_long_kernel(
     if (lane == 0) {
       dqv::VcfSite S;
       const int32_t st = W == U + a
-                             ? dqv::vcf_line_walk(U + a, len, G != 0, contig_table(ctg), &tb, false, &S)
+                             ? dqv::vcf_line_walk(U + a, len, G != 0, ctg, &tb, false, &S)
                              : dqv::vcf_line_walk(slots + (threadIdx.x >> 6) * VCF_WSLOT, len, G != 0,
-                                                  contig_table(ctg), &tb, false, &S);
+                                                  ctg, &tb, false, &S);
       if (st) atomicMin(&scal[0], (unsigned long long)lidx[t] << 8 | (unsigned long long)st);
       else if (S.qual_undecided) atomicAdd(&scal[1], 1ull);
     }
@@ -144,15 +139,8 @@ __device__ inline void store_site(const VcfCols& o, int64_t j, int64_t n, const 
   o.n_info[j] = S.n_info;
   o.n_sample_cols[j] = S.n_sample_cols;
   o.site_len[j] = S.col_end[7];
-  if (S.qual_undecided) {
-    const unsigned long long e = atomicAdd(fix_cnt, 1ull);
-    DQ_CHK((int64_t)e < fix_cap, CHK_VCF);
-    if ((int64_t)e < fix_cap) {  // variant, text offset in U, text length
-      fix[3 * e] = j;
-      fix[3 * e + 1] = text_off + S.col_end[4] + 1;
-      fix[3 * e + 2] = S.col_end[5] - S.col_end[4] - 1;
-    }
-  }
+  if (S.qual_undecided)  // variant, text offset in U, text length
+    fix_append<3>(fix, fix_cap, fix_cnt, {j, text_off + S.col_end[4] + 1, S.col_end[5] - S.col_end[4] - 1});
 }
 
 // a line the validate pass accepted cannot fail here; should it, the row says so and nothing of it
@@ -165,15 +153,11 @@ __device__ inline void blank_site(dqv::VcfSite* S) {
 __global__ __launch_bounds__(256) void vcf_decode_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ vstart,
     const int32_t* __restrict__ vlen, int64_t total, const int64_t* __restrict__ kept, int64_t n,
-    int32_t G, VcfContigs ctg, VcfCols out, int64_t* __restrict__ fix, int64_t fix_cap,
+    int32_t G, dqt::NameTable ctg, VcfCols out, int64_t* __restrict__ fix, int64_t fix_cap,
     unsigned long long* __restrict__ fix_cnt) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[VCF_STAGE];
   const int64_t j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
-  const int64_t jl = j0 + 255 < n ? j0 + 255 : n - 1;  // j0 < n: the grid has no empty block
-  const int64_t tf = kept[j0], tl = kept[jl];
-  DQ_CHK(tf >= 0 && tf < total && tl >= 0 && tl < total, CHK_VCF);
-  const bool listed = tf >= 0 && tf < total && tl >= 0 && tl < total;  // block-uniform
-  const StageSpan sp = stage_span(U, ulen, listed ? vstart[tf] : -1, listed ? vstart[tl] + vlen[tl] : -1, stage);
+  const StageSpan sp = stage_block(VcfLines{U, ulen, vstart, vlen, nullptr, total, kept, n, nullptr}, j0, stage);
   if (j >= n) return;
   const int64_t t = kept[j];
   DQ_CHK(t >= 0 && t < total, CHK_VCF);
@@ -183,11 +167,10 @@ __global__ __launch_bounds__(256) void vcf_decode_kernel(
   const int64_t a = vstart[t];
   DQ_CHK(a >= 0 && len >= 0 && a + len <= ulen, CHK_VCF);
   dqv::VcfSite S;
-  int32_t st;
-  if (sp.staged && a >= sp.lo && a + len <= sp.hi)
-    st = dqv::vcf_line_walk(stage + (a - sp.lo), len, G != 0, contig_table(ctg), nullptr, true, &S);
-  else
-    st = dqv::vcf_line_walk(U + a, len, G != 0, contig_table(ctg), nullptr, true, &S);
+  // two calls: the walk's loads are LDS loads in one and memory loads in the other, not flat ones
+  const int32_t st = in_stage(sp, a, len)
+                         ? dqv::vcf_line_walk(stage + (a - sp.lo), len, G != 0, ctg, nullptr, true, &S)
+                         : dqv::vcf_line_walk(U + a, len, G != 0, ctg, nullptr, true, &S);
   DQ_CHK(st == 0, CHK_VCF);
   if (st) blank_site(&S);
   store_site(out, j, n, S, a, fix, fix_cap, fix_cnt);
@@ -196,7 +179,7 @@ __global__ __launch_bounds__(256) void vcf_decode_kernel(
 __global__ __launch_bounds__(256) void vcf_decode_long_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, const int64_t* __restrict__ vstart,
     const int32_t* __restrict__ vlen, int64_t total, const int64_t* __restrict__ kept, int64_t n,
-    int32_t G, VcfContigs ctg, VcfCols out, int64_t* __restrict__ fix, int64_t fix_cap,
+    int32_t G, dqt::NameTable ctg, VcfCols out, int64_t* __restrict__ fix, int64_t fix_cap,
     unsigned long long* __restrict__ fix_cnt) {
   __shared__ uint8_t slots[4 * VCF_WSLOT];
   const int lane = threadIdx.x & 63;
@@ -214,9 +197,9 @@ __global__ __launch_bounds__(256) void vcf_decode_long_kernel(
     if (lane == 0) {
       dqv::VcfSite S;
       const int32_t st = W == U + a
-                             ? dqv::vcf_line_walk(U + a, len, G != 0, contig_table(ctg), &tb, true, &S)
+                             ? dqv::vcf_line_walk(U + a, len, G != 0, ctg, &tb, true, &S)
                              : dqv::vcf_line_walk(slots + (threadIdx.x >> 6) * VCF_WSLOT, len, G != 0,
-                                                  contig_table(ctg), &tb, true, &S);
+                                                  ctg, &tb, true, &S);
       DQ_CHK(st == 0, CHK_VCF);
       if (st) blank_site(&S);
       store_site(out, j, n, S, a, fix, fix_cap, fix_cnt);
@@ -251,7 +234,7 @@ static unsigned wave_grid(int64_t n) {  // 4 waves per block, grid-stride past 2
 }
 
 void launch_vcf_validate(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
-                         const int64_t* lidx, int64_t n, int32_t G, VcfContigs ctg,
+                         const int64_t* lidx, int64_t n, int32_t G, dqt::NameTable ctg,
                          unsigned long long* scal, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(vcf_validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, U, ulen,
@@ -261,7 +244,7 @@ void launch_vcf_validate(const uint8_t* U, int64_t ulen, const int64_t* vstart, 
 }
 
 void launch_vcf_decode(const uint8_t* U, int64_t ulen, const int64_t* vstart, const int32_t* vlen,
-                       int64_t total, const int64_t* kept, int64_t n, int32_t G, VcfContigs ctg,
+                       int64_t total, const int64_t* kept, int64_t n, int32_t G, dqt::NameTable ctg,
                        VcfCols out, int64_t* fix, int64_t fix_cap, unsigned long long* fix_cnt,
                        hipStream_t s) {
   if (n <= 0) return;

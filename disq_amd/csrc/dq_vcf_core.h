@@ -5,21 +5,16 @@
 // produces, so the validate pass and the decode pass cannot disagree.  Every load of a line lies in
 // [L, L + len).
 #pragma once
-#include <stdint.h>
+#include "dq_text_core.h"
 
-#ifndef __HIPCC__
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#endif
-
-#define DQV_INLINE __host__ __device__ inline
 #ifndef DQV_CHECK  // dq_vcf.hip counts a failed bound here in the bounds-checked build
 #define DQV_CHECK(cond) ((void)0)
 #endif
 
 namespace dqv {
+
+using dqt::is_digit;
+using dqt::NameTable;  // the ##contig IDs, by contig index
 
 // ------------------------------------------------------------------ error classes, in check order
 enum : int32_t {
@@ -53,52 +48,13 @@ enum : uint32_t {
   VCF_REF_LOWER = 128,
 };
 
-// ------------------------------------------------------------------ ##contig IDs
-// hash: FNV-1a of every ID, sorted ascending, ties by contig index (equal IDs resolve to the first);
-// idx: the contig index of each sorted entry; the bytes of contig r are
-// names[name_off[r], name_off[r + 1]).  Built on the host (vcf_contig_table_build).
-struct ContigTable {
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* name_off;
-  const uint8_t* names;
-  int32_t n;
-};
-
-DQV_INLINE uint64_t vcf_name_hash(const uint8_t* p, int32_t n) {
-  uint64_t h = 0xcbf29ce484222325ULL;
-  for (int32_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ULL;
-  return h;
-}
-
-DQV_INLINE int32_t vcf_contig_lookup(const ContigTable& T, const uint8_t* p, int32_t n) {
-  if (T.n <= 0) return -1;
-  const uint64_t h = vcf_name_hash(p, n);
-  int32_t lo = 0, hi = T.n;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (T.hash[mid] < h) lo = mid + 1;
-    else hi = mid;
-  }
-  for (; lo < T.n && T.hash[lo] == h; lo++) {
-    const int32_t r = T.idx[lo];
-    const int32_t a = T.name_off[r];
-    if (T.name_off[r + 1] - a != n) continue;
-    bool eq = true;
-    for (int32_t i = 0; i < n && eq; i++) eq = T.names[a + i] == p[i];
-    if (eq) return r;
-  }
-  return -1;
-}
-
 // ------------------------------------------------------------------ small predicates
-DQV_INLINE bool vcf_digit(uint8_t c) { return c >= '0' && c <= '9'; }
-DQV_INLINE bool vcf_base(uint8_t c) {  // ACGTNacgtn
+DQT_INLINE bool vcf_base(uint8_t c) {  // ACGTNacgtn
   const uint8_t u = c & 0xDF;
   return (c >= 'A') && (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'N');
 }
-DQV_INLINE uint8_t vcf_fold(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
-DQV_INLINE bool vcf_same_nocase(const uint8_t* a, int32_t na, const uint8_t* b, int32_t nb) {
+DQT_INLINE uint8_t vcf_fold(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
+DQT_INLINE bool vcf_same_nocase(const uint8_t* a, int32_t na, const uint8_t* b, int32_t nb) {
   if (na != nb) return false;
   for (int32_t i = 0; i < na; i++)
     if (vcf_fold(a[i]) != vcf_fold(b[i])) return false;
@@ -106,21 +62,9 @@ DQV_INLINE bool vcf_same_nocase(const uint8_t* a, int32_t na, const uint8_t* b, 
 }
 
 // Java Integer.valueOf: [-+]?[0-9]+ with a value in int32.
-DQV_INLINE bool vcf_int32(const uint8_t* t, int32_t n, int32_t* v) {
-  int32_t i = 0;
-  bool neg = false;
-  if (n > 0 && (t[0] == '-' || t[0] == '+')) {
-    neg = t[0] == '-';
-    i = 1;
-  }
-  if (i >= n) return false;
-  int64_t x = 0;
-  for (; i < n; i++) {
-    if (!vcf_digit(t[i])) return false;
-    if (x < (1ll << 40)) x = x * 10 + (t[i] - '0');  // saturates far above the range
-  }
-  if (neg) x = -x;
-  if (x < -2147483648ll || x > 2147483647ll) return false;
+DQT_INLINE bool vcf_int32(const uint8_t* t, int32_t n, int32_t* v) {
+  int64_t x;
+  if (!dqt::parse_dec(t, n, true, -2147483648ll, 2147483647ll, &x)) return false;
   *v = (int32_t)x;
   return true;
 }
@@ -128,7 +72,7 @@ DQV_INLINE bool vcf_int32(const uint8_t* t, int32_t n, int32_t* v) {
 // ------------------------------------------------------------------ QUAL
 enum : int { VCF_Q_OK = 0, VCF_Q_UNDECIDED = 1, VCF_Q_BAD = 2 };
 
-DQV_INLINE double vcf_pow10(int e) {  // 10^e, 0 <= e <= 22: every one a binary64 exactly
+DQT_INLINE double vcf_pow10(int e) {  // 10^e, 0 <= e <= 22: every one a binary64 exactly
   const double t[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
                         1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
   return t[e];
@@ -139,7 +83,7 @@ DQV_INLINE double vcf_pow10(int e) {  // 10^e, 0 <= e <= 22: every one a binary6
 // follow them) and a decimal exponent of that integer in -22..22, so one
 // IEEE multiply or divide of two exact operands rounds correctly; a zero mantissa is zero whatever
 // the exponent.  Every other text is VCF_Q_UNDECIDED (*v = 0): the host converts it with strtod.
-DQV_INLINE int vcf_parse_qual(const uint8_t* t, int32_t n, double* v) {
+DQT_INLINE int vcf_parse_qual(const uint8_t* t, int32_t n, double* v) {
   *v = 0.0;
   int32_t i = 0;
   bool neg = false;
@@ -148,7 +92,7 @@ DQV_INLINE int vcf_parse_qual(const uint8_t* t, int32_t n, double* v) {
   int32_t nsig = 0, drop = 0, nint = 0, nfrac = 0;
   int64_t e10 = 0;
   bool more = false;  // a non-zero digit past the 15th significant one
-  for (; i < n && vcf_digit(t[i]); i++, nint++) {
+  for (; i < n && is_digit(t[i]); i++, nint++) {
     const int d = t[i] - '0';
     if (nsig == 0 && d == 0) continue;
     if (nsig < 15) {
@@ -161,7 +105,7 @@ DQV_INLINE int vcf_parse_qual(const uint8_t* t, int32_t n, double* v) {
   }
   if (i < n && t[i] == '.') {
     i++;
-    for (; i < n && vcf_digit(t[i]); i++, nfrac++) {
+    for (; i < n && is_digit(t[i]); i++, nfrac++) {
       const int d = t[i] - '0';
       if (nsig == 0 && d == 0) {
         if (e10 > -(1 << 20)) e10--;
@@ -184,9 +128,9 @@ DQV_INLINE int vcf_parse_qual(const uint8_t* t, int32_t n, double* v) {
     i++;
     bool eneg = false;
     if (i < n && (t[i] == '-' || t[i] == '+')) eneg = t[i++] == '-';
-    if (i >= n || !vcf_digit(t[i])) return VCF_Q_BAD;
+    if (i >= n || !is_digit(t[i])) return VCF_Q_BAD;
     int64_t ex = 0;
-    for (; i < n && vcf_digit(t[i]); i++)
+    for (; i < n && is_digit(t[i]); i++)
       if (ex < (1 << 20)) ex = ex * 10 + (t[i] - '0');
     e10 += eneg ? -ex : ex;
   }
@@ -227,7 +171,7 @@ struct VcfSite {
 // Walks the value L[0, len) of a data line.  G: the header names a sample.  tabs: the TAB list a
 // wave made, or nullptr (the walk finds them; it counts the TABs past the eighth only when S is
 // wanted in full, want_cols).  Returns VCF_OK and fills *S, or the class of the first failing check.
-DQV_INLINE int32_t vcf_line_walk(const uint8_t* L, int32_t len, bool G, const ContigTable& C,
+DQT_INLINE int32_t vcf_line_walk(const uint8_t* L, int32_t len, bool G, const NameTable& C,
                                  const VcfTabs* tabs, bool want_cols, VcfSite* S) {
   VcfTabs own;
   if (!tabs) {
@@ -263,7 +207,7 @@ DQV_INLINE int32_t vcf_line_walk(const uint8_t* L, int32_t len, bool G, const Co
   S->n_sample_cols = G ? (tabs->total >= 8 ? tabs->total - 8 : 0) : 0;
   // ---- CHROM
   if (ce[0] == 0) return VCF_E_CHROM;
-  S->contig = vcf_contig_lookup(C, L, ce[0]);
+  S->contig = C.n > 0 ? dqt::name_lookup(C, L, ce[0]) : -1;  // no ##contig lines: no hash either
   // ---- POS
   int32_t pos = 0;
   if (!vcf_int32(L + ce[0] + 1, ce[1] - ce[0] - 1, &pos)) return VCF_E_POS;
@@ -387,16 +331,7 @@ DQV_INLINE int32_t vcf_line_walk(const uint8_t* L, int32_t len, bool G, const Co
   return VCF_OK;
 }
 
-}  // namespace dqv
-
 // ------------------------------------------------------------------ host side: the header
-#include <algorithm>
-#include <string>
-#include <utility>
-#include <vector>
-
-namespace dqv {
-
 struct VcfHeader {
   bool has_chrom = false;  // a #CHROM line was seen
   bool has_data = false;   // a line that does not start with '#' follows the header
@@ -452,35 +387,6 @@ inline int vcf_header_parse(const uint8_t* t, int64_t n, bool whole, VcfHeader* 
   }
   if (!whole) return 1;  // only '#' lines so far
   return 0;
-}
-
-struct ContigTableHost {
-  std::vector<uint64_t> hash;
-  std::vector<int32_t> idx, name_off;
-  std::vector<uint8_t> names;
-  ContigTable view() const {
-    return ContigTable{hash.data(), idx.data(), name_off.data(), names.data(), (int32_t)idx.size()};
-  }
-};
-
-inline void vcf_contig_table_build(const std::vector<std::string>& names, ContigTableHost* T) {
-  const size_t n = names.size();
-  T->name_off.assign(1, 0);
-  T->names.clear();
-  std::vector<std::pair<uint64_t, int32_t>> key;
-  for (size_t r = 0; r < n; r++) {
-    T->names.insert(T->names.end(), names[r].begin(), names[r].end());
-    T->name_off.push_back((int32_t)T->names.size());
-    key.push_back({vcf_name_hash((const uint8_t*)names[r].data(), (int32_t)names[r].size()), (int32_t)r});
-  }
-  std::sort(key.begin(), key.end());
-  T->hash.resize(n);
-  T->idx.resize(n);
-  for (size_t i = 0; i < n; i++) {
-    T->hash[i] = key[i].first;
-    T->idx[i] = key[i].second;
-  }
-  T->names.push_back(0);  // never empty
 }
 
 }  // namespace dqv

@@ -10,15 +10,16 @@
 // The header's sample count S chooses the walk: a thread per line below GT_WAVE_S (a block's lines
 // staged in LDS, dq_vcf_stage.h), a wave per line from it on.  Every load of a line lies in
 // [value start, value start + len); every store is guarded by its row (j < n, s < S).
-#include "dq_internal.h"
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DQV_CHECK(cond) DQ_CHK(cond, CHK_VCF)
 #define DQG_CHECK(cond) DQ_CHK(cond, CHK_VCF)
+#define DQT_CHECK(cond) DQ_CHK(cond, CHK_VCF)
 #else
 #define DQV_CHECK(cond) ((void)0)
 #define DQG_CHECK(cond) ((void)0)
+#define DQT_CHECK(cond) ((void)0)
 #endif
+#include "dq_internal.h"
 #include "dq_vcf_gt_core.h"
 #include "dq_vcf_stage.h"
 
@@ -45,13 +46,7 @@ struct HostGqList {  // fix-up entries: cell, text offset in U, text length
   unsigned long long* cnt;
   int64_t cell0, text0;
   __device__ void operator()(int32_t s, int32_t at, int32_t len) const {
-    const unsigned long long e = atomicAdd(cnt, 1ull);
-    DQ_CHK((int64_t)e < cap, CHK_VCF);
-    if ((int64_t)e < cap) {
-      fix[3 * e] = cell0 + s;
-      fix[3 * e + 1] = text0 + at;
-      fix[3 * e + 2] = len;
-    }
+    fix_append<3>(fix, cap, cnt, {cell0 + s, text0 + at, len});
   }
 };
 
@@ -85,15 +80,11 @@ struct GtLineAt {
   int32_t len, fmt_at, n_alt, nsc;
 };
 __device__ inline bool line_at(const GtIn& in, int64_t j, GtLineAt* A) {
-  A->t = in.kept[j];
-  DQ_CHK(A->t >= 0 && A->t < in.total, CHK_VCF);
-  if (A->t < 0 || A->t >= in.total) return false;
-  A->a = in.vstart[A->t];
-  A->len = in.vlen[A->t];
-  A->fmt_at = in.col_end[8 * j + 7] + 1;
+  if (!kept_line(in.ln, j, &A->t, &A->a, &A->len)) return false;
+  A->fmt_at = in.ln.col_end[8 * j + 7] + 1;
   A->n_alt = in.n_alt[j];
   A->nsc = in.n_sample_cols[j];
-  const bool ok = A->a >= 0 && A->len >= 0 && A->a + A->len <= in.ulen && A->fmt_at >= 1 && A->fmt_at <= A->len;
+  const bool ok = line_in_u(in.ln, A->a, A->len) && A->fmt_at >= 1 && A->fmt_at <= A->len;
   DQ_CHK(ok, CHK_VCF);
   return ok;
 }
@@ -104,17 +95,12 @@ __global__ __launch_bounds__(256) void gt_thread_kernel(GtIn in, GtCols out, int
                                                          unsigned long long* __restrict__ scal,
                                                          int64_t* __restrict__ fix, int64_t fix_cap) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[VCF_STAGE];
-  const int64_t n = in.n, j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
-  const int64_t jl = j0 + 255 < n ? j0 + 255 : n - 1;  // j0 < n: the grid has no empty block
-  const int64_t tf = in.kept[j0], tl = in.kept[jl];
-  DQ_CHK(tf >= 0 && tf < in.total && tl >= 0 && tl < in.total, CHK_VCF);
-  const bool listed = tf >= 0 && tf < in.total && tl >= 0 && tl < in.total;  // block-uniform
-  const StageSpan sp = stage_span(in.U, in.ulen, listed ? in.vstart[tf] : -1,
-                                  listed ? in.vstart[tl] + in.vlen[tl] : -1, stage);
+  const int64_t j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
+  const StageSpan sp = stage_block(in.ln, j0, stage);
   int32_t maxp = 0;
   GtLineAt A;
-  if (j < n && line_at(in, j, &A)) {
-    const uint8_t* L = sp.staged && A.a >= sp.lo && A.a + A.len <= sp.hi ? stage + (A.a - sp.lo) : in.U + A.a;
+  if (j < in.ln.n && line_at(in, j, &A)) {
+    const uint8_t* L = stage_line(sp, stage, in.ln.U, A.a, A.len);
     if (DEC) {
       const dqg::GtLine R = dqg::gt_line_walk(L, A.len, A.fmt_at, in.S, A.nsc, A.n_alt, P, row_of(out, j, in.S, P),
                                     HostGqList{fix, fix_cap, scal + 3, j * in.S, A.a});
@@ -128,7 +114,7 @@ __global__ __launch_bounds__(256) void gt_thread_kernel(GtIn in, GtCols out, int
       const dqg::GtLine R =
           dqg::gt_line_walk(L, A.len, A.fmt_at, in.S, A.nsc, A.n_alt, 0, dqg::GtRow{}, HostGqCount{&nhost});
       if (R.st) {
-        atomicMin(&scal[0], dqg::gt_error_key(in.lidx[A.t], R.sample, R.st));
+        atomicMin(&scal[0], dqg::gt_error_key(in.ln.lidx[A.t], R.sample, R.st));
       } else {
         maxp = R.max_ploidy;
         if (nhost) atomicAdd(&scal[2], (unsigned long long)nhost);
@@ -161,16 +147,16 @@ __global__ __launch_bounds__(256) void gt_wave_kernel(GtIn in, GtCols out, int32
   const int64_t nwave = (int64_t)gridDim.x * 4;
   const int32_t S = in.S;
   int32_t maxp = 0;
-  for (int64_t j = (int64_t)blockIdx.x * 4 + w; j < in.n; j += nwave) {
+  for (int64_t j = (int64_t)blockIdx.x * 4 + w; j < in.ln.n; j += nwave) {
     GtLineAt A;
     if (!line_at(in, j, &A)) continue;  // wave-uniform
     if (A.nsc != S) {                   // wave-uniform
       DQ_CHK(!DEC, CHK_VCF);
-      if (!DEC && lane == 0) atomicMin(&scal[0], dqg::gt_error_key(in.lidx[A.t], 0, dqg::GT_E_SAMPLES));
+      if (!DEC && lane == 0) atomicMin(&scal[0], dqg::gt_error_key(in.ln.lidx[A.t], 0, dqg::GT_E_SAMPLES));
       continue;
     }
     // positions from here on count from the FORMAT column's first byte
-    const uint8_t* T = in.U + A.a + A.fmt_at;
+    const uint8_t* T = in.ln.U + A.a + A.fmt_at;
     const int32_t tl = A.len - A.fmt_at;
     const bool staged = tl <= GT_WSLOT;  // wave-uniform
     const uint8_t* W = staged ? slot : T;
@@ -201,7 +187,7 @@ __global__ __launch_bounds__(256) void gt_wave_kernel(GtIn in, GtCols out, int32
         const int32_t st = dqg::gt_format_parse(W, 0, offs[0] - 1, &F);
         if (st) {
           DQ_CHK(!DEC, CHK_VCF);
-          if (!DEC && lane == 0) atomicMin(&scal[0], dqg::gt_error_key(in.lidx[A.t], 0, st));
+          if (!DEC && lane == 0) atomicMin(&scal[0], dqg::gt_error_key(in.ln.lidx[A.t], 0, st));
           break;
         }
         have_fmt = true;
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(256) void gt_wave_kernel(GtIn in, GtCols out, int32
           out.dp[cell] = C.dp;
           out.cell_off[cell] = A.fmt_at + ca;
         } else if (st) {
-          atomicMin(&scal[0], dqg::gt_error_key(in.lidx[A.t], s, st));
+          atomicMin(&scal[0], dqg::gt_error_key(in.ln.lidx[A.t], s, st));
           bad = true;
         } else {
           maxp = C.ploidy > maxp ? C.ploidy : maxp;
@@ -263,12 +249,12 @@ DQ_CHK_UNIT(vcfgt)
 template <bool DEC>
 static void launch_gt(GtIn in, GtCols out, int32_t P, unsigned long long* scal, int64_t* fix,
                       int64_t fix_cap, hipStream_t s) {
-  if (in.n <= 0 || in.S <= 0) return;
+  if (in.ln.n <= 0 || in.S <= 0) return;
   if (in.S < GT_WAVE_S) {
-    hipLaunchKernelGGL(gt_thread_kernel<DEC>, dim3((unsigned)((in.n + 255) / 256)), dim3(256), 0, s, in, out,
+    hipLaunchKernelGGL(gt_thread_kernel<DEC>, dim3((unsigned)((in.ln.n + 255) / 256)), dim3(256), 0, s, in, out,
                        P, scal, fix, fix_cap);
   } else {  // 4 waves per block, grid-stride past 2048 blocks
-    const int64_t g = (in.n + 3) / 4;
+    const int64_t g = (in.ln.n + 3) / 4;
     hipLaunchKernelGGL(gt_wave_kernel<DEC>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, in, out,
                        P, scal, fix, fix_cap);
   }

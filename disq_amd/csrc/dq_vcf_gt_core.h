@@ -14,7 +14,7 @@
 
 namespace dqg {
 
-using dqv::vcf_digit;
+using dqt::is_digit;
 using dqv::vcf_int32;
 
 // ------------------------------------------------------------------ error classes, in check order
@@ -41,7 +41,7 @@ constexpr int32_t GT_MAX_ALLELE = 32767;
 
 // The first failing (line, sample, class) as one word a minimum orders: the line index above the
 // sample above the class; a line-level class (samples, FORMAT) carries sample 0.
-DQV_INLINE unsigned long long gt_error_key(int64_t line, int32_t sample, int32_t st) {
+DQT_INLINE unsigned long long gt_error_key(int64_t line, int32_t sample, int32_t st) {
   return (unsigned long long)line << 32 | (unsigned long long)(uint32_t)sample << 8 | (unsigned long long)st;
 }
 
@@ -53,7 +53,7 @@ struct GtFormat {
 };
 
 // Column 9 = L[a, z).  An empty column, GT anywhere but first and GT, GQ, DP or FT twice fail.
-DQV_INLINE int32_t gt_format_parse(const uint8_t* L, int32_t a, int32_t z, GtFormat* F) {
+DQT_INLINE int32_t gt_format_parse(const uint8_t* L, int32_t a, int32_t z, GtFormat* F) {
   F->nkeys = 0;
   F->gt = 0;
   F->gq = F->dp = F->ft = -1;
@@ -91,12 +91,12 @@ DQV_INLINE int32_t gt_format_parse(const uint8_t* L, int32_t a, int32_t z, GtFor
 // (int) Math.round(Double.valueOf(text)) rounds their binary64: text and tie point (k + 0.5) both
 // have at most 15 significant digits, so the conversion to binary64, which is monotonic and maps
 // decimals of up to 15 digits one to one, cannot move the text's value across the tie.
-DQV_INLINE bool gt_gq_digits(const uint8_t* t, int32_t n, int32_t* v) {
+DQT_INLINE bool gt_gq_digits(const uint8_t* t, int32_t n, int32_t* v) {
   int32_t i = 0;
   bool neg = false;
   if (i < n && (t[i] == '-' || t[i] == '+')) neg = t[i++] == '-';
   int32_t ip = 0, ni = 0;
-  for (; i < n && vcf_digit(t[i]); i++, ni++) {
+  for (; i < n && is_digit(t[i]); i++, ni++) {
     if (ni >= 9) return false;
     ip = ip * 10 + (t[i] - '0');
   }
@@ -105,7 +105,7 @@ DQV_INLINE bool gt_gq_digits(const uint8_t* t, int32_t n, int32_t* v) {
   bool rest = false;  // a non-zero digit past the first fractional one
   if (i < n && t[i] == '.') {
     i++;
-    for (; i < n && vcf_digit(t[i]); i++, nf++) {
+    for (; i < n && is_digit(t[i]); i++, nf++) {
       if (nf >= 6) return false;
       if (nf == 0) first = t[i] - '0';
       else rest |= t[i] != '0';
@@ -143,7 +143,7 @@ struct GtCell {
   int32_t gq_at, gq_len;   // that text, as an offset from L
 };
 
-DQV_INLINE void gt_cell_blank(GtCell* C) {
+DQT_INLINE void gt_cell_blank(GtCell* C) {
   C->flags = 0;
   C->ploidy = 0;
   C->gq = C->dp = -1;
@@ -154,7 +154,7 @@ DQV_INLINE void gt_cell_blank(GtCell* C) {
 // The sample column L[a, z) under the keys F of a line with n_alt ALT alleles.  al: nullptr, or P
 // slots that take the allele indices (-1 a no-call, -2 past the ploidy).  Returns GT_OK and fills
 // *C, or the class of the first failing check in the order cell, GT, GQ, DP.
-DQV_INLINE int32_t gt_cell(const uint8_t* L, int32_t a, int32_t z, const GtFormat& F, int32_t n_alt,
+DQT_INLINE int32_t gt_cell(const uint8_t* L, int32_t a, int32_t z, const GtFormat& F, int32_t n_alt,
                            int16_t* al, int32_t P, GtCell* C) {
   gt_cell_blank(C);
   DQG_CHECK(a >= 0 && a <= z);
@@ -259,7 +259,7 @@ struct GtLine {
 // host_gq(sample, text offset, text length) is called for every GQ text left to the host.  The way
 // a thread of dq_vcf_gt.hip and the host walk a line; a wave shares the cells among its lanes.
 template <typename HostGq>
-DQV_INLINE GtLine gt_line_walk(const uint8_t* L, int32_t len, int32_t fmt_at, int32_t S, int32_t nsc,
+DQT_INLINE GtLine gt_line_walk(const uint8_t* L, int32_t len, int32_t fmt_at, int32_t S, int32_t nsc,
                                int32_t n_alt, int32_t P, const GtRow& row, HostGq&& host_gq) {
   GtLine R{GT_OK, 0, 0};
   if (nsc != S) {

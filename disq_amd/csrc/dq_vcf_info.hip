@@ -15,15 +15,16 @@
 // and element index.
 #include <cstdlib>
 
-#include "dq_internal.h"
-
 #if defined(__HIP_DEVICE_COMPILE__)
 #define DQV_CHECK(cond) DQ_CHK(cond, CHK_VCF)
 #define DQI_CHECK(cond) DQ_CHK(cond, CHK_VCF)
+#define DQT_CHECK(cond) DQ_CHK(cond, CHK_VCF)
 #else
 #define DQV_CHECK(cond) ((void)0)
 #define DQI_CHECK(cond) ((void)0)
+#define DQT_CHECK(cond) ((void)0)
 #endif
+#include "dq_internal.h"
 #include "dq_vcf_info_core.h"
 #include "dq_vcf_stage.h"
 
@@ -52,28 +53,29 @@ struct KeyLds {
 };
 
 // out: the decode pass's columns (their bases and widths), or nullptr.  Ends in a block barrier.
-__device__ inline void keys_load(KeyLds& K, const InfoKeysDev& k, const InfoCols* out) {
+__device__ inline void keys_load(KeyLds& K, const InfoIn& in, const InfoCols* out) {
+  const dqt::NameTable& k = in.keys;
   const int t = threadIdx.x;
   if (t < 64) {
-    const bool in = t < k.n;
-    K.hash[t] = in ? k.hash[t] : ~0ull;
-    K.idx[t] = in ? k.idx[t] : 0;
-    K.type[t] = in ? k.type[t] : 0;
-    K.hflag[t] = in ? k.hflag[t] : 0;
-    K.base[t] = in && out ? out->key_base[t] : -1;
-    K.width[t] = in && out ? out->key_width[t] : 0;
+    const bool on = t < k.n;
+    K.hash[t] = on ? k.hash[t] : ~0ull;
+    K.idx[t] = on ? k.idx[t] : 0;
+    K.type[t] = on ? in.key_type[t] : 0;
+    K.hflag[t] = on ? in.key_hflag[t] : 0;
+    K.base[t] = on && out ? out->key_base[t] : -1;
+    K.width[t] = on && out ? out->key_width[t] : 0;
   }
-  if (t < 65) K.id_off[t] = t <= k.n ? k.id_off[t] : 0;
-  const int32_t nb = k.n >= 0 && k.n <= 64 ? k.id_off[k.n] : 0;  // block-uniform
+  if (t < 65) K.id_off[t] = t <= k.n ? k.name_off[t] : 0;
+  const int32_t nb = k.n >= 0 && k.n <= 64 ? k.name_off[k.n] : 0;  // block-uniform
   if (nb <= INFO_IDS_LDS)
-    for (int32_t i = t; i < nb; i += (int32_t)blockDim.x) K.ids[i] = k.ids[i];
+    for (int32_t i = t; i < nb; i += (int32_t)blockDim.x) K.ids[i] = k.names[i];
   __syncthreads();
 }
 
-__device__ inline dqi::InfoKeys keys_view(const KeyLds& K, const InfoKeysDev& k) {
+__device__ inline dqi::InfoKeys keys_view(const KeyLds& K, const dqt::NameTable& k) {
   const int32_t n = k.n < 64 ? k.n : 64;
   const bool in_lds = n >= 0 && K.id_off[n] <= INFO_IDS_LDS;  // as keys_load decided
-  return dqi::InfoKeys{K.hash, K.idx, K.id_off, in_lds ? K.ids : k.ids, K.type, K.hflag, n};
+  return dqi::InfoKeys{{K.hash, K.idx, K.id_off, in_lds ? K.ids : k.names, n}, K.type, K.hflag};
 }
 
 struct CheckSink {
@@ -124,15 +126,7 @@ struct DecodeSink {
     if (ok) o.fval[e] = bits;
   }
   __device__ void host(int32_t q, int32_t j, int32_t at, int32_t len) {
-    const unsigned long long e = atomicAdd(cnt, 1ull);
-    DQ_CHK((int64_t)e < fix_cap, CHK_VCF);
-    if ((int64_t)e < fix_cap) {
-      fix[5 * e] = q;
-      fix[5 * e + 1] = k;
-      fix[5 * e + 2] = j;
-      fix[5 * e + 3] = text0 + off0 + at;
-      fix[5 * e + 4] = len;
-    }
+    fix_append<5>(fix, fix_cap, cnt, {q, k, j, text0 + off0 + at, len});
   }
   __device__ void cell(int32_t q, const dqi::InfoCell& C) {
     if (!row(q)) return;
@@ -159,14 +153,10 @@ struct InfoLineAt {
   int32_t len, ia, iz;
 };
 __device__ inline bool line_at(const InfoIn& in, int64_t j, InfoLineAt* A) {
-  A->t = in.kept[j];
-  DQ_CHK(A->t >= 0 && A->t < in.total, CHK_VCF);
-  if (A->t < 0 || A->t >= in.total) return false;
-  A->a = in.vstart[A->t];
-  A->len = in.vlen[A->t];
-  A->ia = in.col_end[8 * j + 6] + 1;
-  A->iz = in.col_end[8 * j + 7];
-  const bool ok = A->a >= 0 && A->len >= 0 && A->a + A->len <= in.ulen && A->ia >= 1 && A->ia <= A->iz && A->iz <= A->len;
+  if (!kept_line(in.ln, j, &A->t, &A->a, &A->len)) return false;
+  A->ia = in.ln.col_end[8 * j + 6] + 1;
+  A->iz = in.ln.col_end[8 * j + 7];
+  const bool ok = line_in_u(in.ln, A->a, A->len) && A->ia >= 1 && A->ia <= A->iz && A->iz <= A->len;
   DQ_CHK(ok, CHK_VCF);
   return ok;
 }
@@ -180,27 +170,22 @@ __global__ __launch_bounds__(256) void info_thread_kernel(InfoIn in, InfoCols ou
                                                            int32_t wave_at) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[VCF_STAGE];
   __shared__ KeyLds K;
-  keys_load(K, in.keys, DEC ? &out : nullptr);
-  const int64_t n = in.n, j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
-  const int64_t jl = j0 + 255 < n ? j0 + 255 : n - 1;  // j0 < n: the grid has no empty block
-  const int64_t tf = in.kept[j0], tl = in.kept[jl];
-  DQ_CHK(tf >= 0 && tf < in.total && tl >= 0 && tl < in.total, CHK_VCF);
-  const bool listed = tf >= 0 && tf < in.total && tl >= 0 && tl < in.total;  // block-uniform
-  const StageSpan sp = stage_span(in.U, in.ulen, listed ? in.vstart[tf] : -1,
-                                  listed ? in.vstart[tl] + in.vlen[tl] : -1, stage);
+  keys_load(K, in, DEC ? &out : nullptr);
+  const int64_t n = in.ln.n, j0 = (int64_t)blockIdx.x * 256, j = j0 + threadIdx.x;
+  const StageSpan sp = stage_block(in.ln, j0, stage);
   InfoLineAt A;
   if (j >= n || !line_at(in, j, &A) || A.iz - A.ia > wave_at) return;  // the longer ones: info_wave_kernel
-  const uint8_t* L = sp.staged && A.a >= sp.lo && A.a + A.len <= sp.hi ? stage + (A.a - sp.lo) : in.U + A.a;
+  const uint8_t* L = stage_line(sp, stage, in.ln.U, A.a, A.len);
   const dqi::InfoKeys T = keys_view(K, in.keys);
   if (DEC) {
-    DecodeSink sink{out, K, T.n, n, j, A.a, 0, fix, fix_cap, scal + 2};
+    DecodeSink sink{out, K, T.tab.n, n, j, A.a, 0, fix, fix_cap, scal + 2};
     const int32_t bad = dqi::info_line_walk(L, A.ia, A.iz, T, sink);
     (void)bad;
     DQ_CHK(bad < 0, CHK_VCF);  // the check pass accepted the line (a failing cell is stored blank)
   } else {
-    CheckSink sink{width, T.n, 0};
+    CheckSink sink{width, T.tab.n, 0};
     const int32_t bad = dqi::info_line_walk(L, A.ia, A.iz, T, sink);
-    if (bad >= 0) atomicMin(&scal[0], dqi::info_error_key(in.lidx[A.t], bad));
+    if (bad >= 0) atomicMin(&scal[0], dqi::info_error_key(in.ln.lidx[A.t], bad));
     else if (sink.nhost) atomicAdd(&scal[1], (unsigned long long)sink.nhost);
   }
 }
@@ -223,18 +208,18 @@ __global__ __launch_bounds__(256) void info_wave_kernel(InfoIn in, InfoCols out,
   __shared__ KeyLds K;
   __shared__ int32_t first_all[4 * 64], cnt_all[4 * 64];
   __shared__ uint8_t slots[4 * INFO_WSLOT];
-  keys_load(K, in.keys, DEC ? &out : nullptr);
+  keys_load(K, in, DEC ? &out : nullptr);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int32_t* first = first_all + w * 64;
   int32_t* cnt = cnt_all + w * 64;
   uint8_t* slot = slots + w * INFO_WSLOT;
   const dqi::InfoKeys T = keys_view(K, in.keys);
-  const int64_t nchunk = (in.n + 63) / 64, nwave = (int64_t)gridDim.x * 4;
+  const int64_t nchunk = (in.ln.n + 63) / 64, nwave = (int64_t)gridDim.x * 4;
   int32_t nhost = 0;
   for (int64_t c = (int64_t)blockIdx.x * 4 + w; c < nchunk; c += nwave) {
     const int64_t jm = c * 64 + lane;
     int32_t mylen = 0;
-    if (jm < in.n) mylen = in.col_end[8 * jm + 7] - in.col_end[8 * jm + 6] - 1;
+    if (jm < in.ln.n) mylen = in.ln.col_end[8 * jm + 7] - in.ln.col_end[8 * jm + 6] - 1;
     unsigned long long m = __ballot(mylen > wave_at);
     while (m) {  // wave-uniform
       const int64_t j = c * 64 + (int64_t)__builtin_ctzll(m);
@@ -242,7 +227,7 @@ __global__ __launch_bounds__(256) void info_wave_kernel(InfoIn in, InfoCols out,
       InfoLineAt A;
       if (!line_at(in, j, &A)) continue;
       // positions from here on count from the INFO column's first byte
-      const uint8_t* P = in.U + A.a + A.ia;
+      const uint8_t* P = in.ln.U + A.a + A.ia;
       const int32_t il = A.iz - A.ia;
       const bool staged = il <= INFO_WSLOT;  // wave-uniform
       first[lane] = 0x7fffffff;
@@ -255,7 +240,7 @@ __global__ __launch_bounds__(256) void info_wave_kernel(InfoIn in, InfoCols out,
         if (staged) slot[x] = P[x];
         if (x == 0 || P[x - 1] == ';') {
           const int32_t ke = dqi::info_key_end(P, x, il);
-          const int32_t q = dqi::info_lookup(T, P + x, ke - x);
+          const int32_t q = dqt::name_lookup(T.tab, P + x, ke - x);
           if (q >= 0) {
             atomicMin(&first[q], x);
             atomicAdd(&cnt[q], 1);
@@ -265,14 +250,14 @@ __global__ __launch_bounds__(256) void info_wave_kernel(InfoIn in, InfoCols out,
       // the wave's LDS stores and atomics above are read by other lanes below
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (lane < T.n) {
+      if (lane < T.tab.n) {
         const int32_t q = lane, f = first[q];
         const uint8_t* W = staged ? slot : P;
         dqi::InfoCell C = dqi::info_blank();
         const bool has = f >= 0 && f < il;
         DQ_CHK(has || f == 0x7fffffff, CHK_VCF);
         if (DEC) {
-          DecodeSink sink{out, K, T.n, in.n, j, A.a, A.ia, fix, fix_cap, scal + 2};
+          DecodeSink sink{out, K, T.tab.n, in.ln.n, j, A.a, A.ia, fix, fix_cap, scal + 2};
           if (has) {
             const int32_t ke = dqi::info_key_end(W, f, il);
             const int32_t pe = ke < il && W[ke] == '=' ? dqi::info_piece_end(W, ke, il) : ke;
@@ -284,12 +269,12 @@ __global__ __launch_bounds__(256) void info_wave_kernel(InfoIn in, InfoCols out,
           sink.cell(q, C);
           if (has && cnt[q] > 1) sink.repeated(q);
         } else if (has) {
-          CheckSink sink{width, T.n, 0};
+          CheckSink sink{width, T.tab.n, 0};
           const int32_t ke = dqi::info_key_end(W, f, il);
           const int32_t pe = ke < il && W[ke] == '=' ? dqi::info_piece_end(W, ke, il) : ke;
           dqi::InfoKeySink<CheckSink> ks{sink, q};
           if (!dqi::info_cell(W, ke, pe, K.type[q], K.hflag[q] != 0, &C, ks))
-            atomicMin(&scal[0], dqi::info_error_key(in.lidx[A.t], q));
+            atomicMin(&scal[0], dqi::info_error_key(in.ln.lidx[A.t], q));
           else
             nhost += sink.nhost;
           sink.cell(q, C);
@@ -321,10 +306,10 @@ static int32_t info_wave_at() {
 template <bool DEC>
 static void launch_info(InfoIn in, InfoCols out, unsigned long long* scal, int32_t* width, int64_t* fix,
                         int64_t fix_cap, hipStream_t s) {
-  if (in.n <= 0 || in.keys.n <= 0 || in.keys.n > dqi::INFO_MAX_KEYS) return;
-  hipLaunchKernelGGL(info_thread_kernel<DEC>, dim3((unsigned)((in.n + 255) / 256)), dim3(256), 0, s, in, out,
+  if (in.ln.n <= 0 || in.keys.n <= 0 || in.keys.n > dqi::INFO_MAX_KEYS) return;
+  hipLaunchKernelGGL(info_thread_kernel<DEC>, dim3((unsigned)((in.ln.n + 255) / 256)), dim3(256), 0, s, in, out,
                      scal, width, fix, fix_cap, info_wave_at());
-  const int64_t g = ((in.n + 63) / 64 + 3) / 4;  // 4 waves per block, 64 variants a wave and step
+  const int64_t g = ((in.ln.n + 63) / 64 + 3) / 4;  // 4 waves per block, 64 variants a wave and step
   hipLaunchKernelGGL(info_wave_kernel<DEC>, dim3((unsigned)(g > 2048 ? 2048 : g)), dim3(256), 0, s, in, out,
                      scal, width, fix, fix_cap, info_wave_at());
 }

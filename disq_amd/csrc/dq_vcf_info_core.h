@@ -27,47 +27,22 @@ constexpr uint64_t INFO_F_NAN_BITS = 0x7ff8000000000000ull;      // Java's Doubl
 constexpr uint64_t INFO_F_INF_BITS = 0x7ff0000000000000ull;
 
 // ------------------------------------------------------------------ the requested keys
-// hash: vcf_name_hash of every id, sorted ascending; idx: the key index of each sorted entry; the
-// bytes of key q are ids[id_off[q], id_off[q + 1]); type: the resolved conversion type of key q;
-// hflag: the header's ##INFO line types key q as Flag.  Built on the host (info_key_table_build).
+// tab: the ids as a name table (dq_text_core.h), key q its name q; type: the resolved conversion
+// type of key q; hflag: the header's ##INFO line types key q as Flag.  Built on the host
+// (info_key_table_build).
 struct InfoKeys {
-  const uint64_t* hash;
-  const int32_t* idx;
-  const int32_t* id_off;
-  const uint8_t* ids;
+  dqt::NameTable tab;
   const uint8_t* type;
   const uint8_t* hflag;
-  int32_t n;
 };
-
-// The index of the requested key equal to p[0, n) byte for byte, or -1.
-DQV_INLINE int32_t info_lookup(const InfoKeys& T, const uint8_t* p, int32_t n) {
-  const uint64_t h = dqv::vcf_name_hash(p, n);
-  int32_t lo = 0, hi = T.n;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (T.hash[mid] < h) lo = mid + 1;
-    else hi = mid;
-  }
-  for (; lo < T.n && T.hash[lo] == h; lo++) {
-    const int32_t q = T.idx[lo];
-    DQI_CHECK(q >= 0 && q < T.n);
-    const int32_t a = T.id_off[q];
-    if (T.id_off[q + 1] - a != n) continue;
-    bool eq = true;
-    for (int32_t i = 0; i < n && eq; i++) eq = T.ids[a + i] == p[i];
-    if (eq) return q;
-  }
-  return -1;
-}
 
 // ------------------------------------------------------------------ one cell
 struct InfoCell {
   int32_t flags, n_values, val_off, val_len;
 };
-DQV_INLINE InfoCell info_blank() { return InfoCell{0, 0, -1, 0}; }
+DQT_INLINE InfoCell info_blank() { return InfoCell{0, 0, -1, 0}; }
 
-DQV_INLINE bool info_is(const uint8_t* t, int32_t n, const char* w, int32_t wn) {
+DQT_INLINE bool info_is(const uint8_t* t, int32_t n, const char* w, int32_t wn) {
   if (n != wn) return false;
   for (int32_t i = 0; i < n; i++)
     if (t[i] != (uint8_t)w[i]) return false;
@@ -76,7 +51,7 @@ DQV_INLINE bool info_is(const uint8_t* t, int32_t n, const char* w, int32_t wn) 
 
 // One element of a Float value: '.', the QUAL grammar, or Java Double.valueOf's NaN, Infinity,
 // +Infinity, -Infinity.  0: *bits holds the value; 1: the host's strtod converts it; 2: refused.
-DQV_INLINE int info_float(const uint8_t* t, int32_t n, uint64_t* bits) {
+DQT_INLINE int info_float(const uint8_t* t, int32_t n, uint64_t* bits) {
   *bits = INFO_F_MISSING_BITS;
   if (n == 1 && t[0] == '.') return 0;
   if (n >= 3 && (t[0] == 'N' || t[0] == 'I' || t[1] == 'I')) {
@@ -101,7 +76,7 @@ DQV_INLINE int info_float(const uint8_t* t, int32_t n, uint64_t* bits) {
 // elements go to the sink (ival(j, v) / fval(j, bits) / host(j, at, len): element j is left to the
 // host's strtod, text L[at, at + len)); false at the first element that fails its grammar.
 template <class Sink>
-DQV_INLINE bool info_values(const uint8_t* L, int32_t va, int32_t vz, int32_t type, int32_t* nv, Sink& sink) {
+DQT_INLINE bool info_values(const uint8_t* L, int32_t va, int32_t vz, int32_t type, int32_t* nv, Sink& sink) {
   int32_t j = 0;
   for (int32_t b = va;;) {
     int32_t e = b;
@@ -131,7 +106,7 @@ DQV_INLINE bool info_values(const uint8_t* L, int32_t va, int32_t vz, int32_t ty
 // The piece L[.., pe) whose key ends at ke (ke == pe: no '='), for a key of conversion `type` that
 // the header types as Flag or not (hflag).  False when a value fails its grammar (*C blank then).
 template <class Sink>
-DQV_INLINE bool info_cell(const uint8_t* L, int32_t ke, int32_t pe, int32_t type, bool hflag, InfoCell* C,
+DQT_INLINE bool info_cell(const uint8_t* L, int32_t ke, int32_t pe, int32_t type, bool hflag, InfoCell* C,
                           Sink& sink) {
   *C = info_blank();
   if (ke >= pe) {  // no '=': in the map (true for a Flag, the missing value otherwise)
@@ -151,12 +126,12 @@ DQV_INLINE bool info_cell(const uint8_t* L, int32_t ke, int32_t pe, int32_t type
 }
 
 // the end of the key that starts at b: the first '=' or ';' or z
-DQV_INLINE int32_t info_key_end(const uint8_t* L, int32_t b, int32_t z) {
+DQT_INLINE int32_t info_key_end(const uint8_t* L, int32_t b, int32_t z) {
   int32_t e = b;
   while (e < z && L[e] != '=' && L[e] != ';') e++;
   return e;
 }
-DQV_INLINE int32_t info_piece_end(const uint8_t* L, int32_t b, int32_t z) {
+DQT_INLINE int32_t info_piece_end(const uint8_t* L, int32_t b, int32_t z) {
   int32_t e = b;
   while (e < z && L[e] != ';') e++;
   return e;
@@ -166,9 +141,9 @@ template <class Sink>
 struct InfoKeySink {  // a line sink seen from one key's cell
   Sink& s;
   int32_t q;
-  DQV_INLINE void ival(int32_t j, int32_t v) { s.ival(q, j, v); }
-  DQV_INLINE void fval(int32_t j, uint64_t bits) { s.fval(q, j, bits); }
-  DQV_INLINE void host(int32_t j, int32_t at, int32_t len) { s.host(q, j, at, len); }
+  DQT_INLINE void ival(int32_t j, int32_t v) { s.ival(q, j, v); }
+  DQT_INLINE void fval(int32_t j, uint64_t bits) { s.fval(q, j, bits); }
+  DQT_INLINE void host(int32_t j, int32_t at, int32_t len) { s.host(q, j, at, len); }
 };
 
 // ------------------------------------------------------------------ the line walk
@@ -177,7 +152,7 @@ struct InfoKeySink {  // a line sink seen from one key's cell
 // its elements (sink.ival / fval / host, see info_values), and sink.repeated(q) behind that when
 // a later piece has the same key.  Returns the lowest index of a key whose value failed, or -1.
 template <class Sink>
-DQV_INLINE int32_t info_line_walk(const uint8_t* L, int32_t a, int32_t z, const InfoKeys& T, Sink& sink) {
+DQT_INLINE int32_t info_line_walk(const uint8_t* L, int32_t a, int32_t z, const InfoKeys& T, Sink& sink) {
   uint64_t seen = 0, rep = 0;
   int32_t bad = -1;
   if (!(z - a == 1 && L[a] == '.')) {
@@ -185,7 +160,7 @@ DQV_INLINE int32_t info_line_walk(const uint8_t* L, int32_t a, int32_t z, const 
       DQI_CHECK(b >= a && b < z);
       const int32_t ke = info_key_end(L, b, z);
       const int32_t pe = ke < z && L[ke] == '=' ? info_piece_end(L, ke, z) : ke;
-      const int32_t q = info_lookup(T, L + b, ke - b);
+      const int32_t q = dqt::name_lookup(T.tab, L + b, ke - b);
       if (q >= 0) {
         const uint64_t bit = 1ull << q;
         if (seen & bit) {
@@ -201,7 +176,7 @@ DQV_INLINE int32_t info_line_walk(const uint8_t* L, int32_t a, int32_t z, const 
       b = pe + 1;
     }
   }
-  for (int32_t q = 0; q < T.n; q++) {
+  for (int32_t q = 0; q < T.tab.n; q++) {
     if (!(seen >> q & 1)) sink.cell(q, info_blank());
     else if (rep >> q & 1) sink.repeated(q);
   }
@@ -209,7 +184,7 @@ DQV_INLINE int32_t info_line_walk(const uint8_t* L, int32_t a, int32_t z, const 
 }
 
 // first offender: the lowest line, then the lowest key index
-DQV_INLINE unsigned long long info_error_key(int64_t line, int32_t q) {
+DQT_INLINE unsigned long long info_error_key(int64_t line, int32_t q) {
   return (unsigned long long)line << 8 | (unsigned long long)(q & 0xff);
 }
 
@@ -253,12 +228,9 @@ inline void info_header_types(const uint8_t* t, int64_t n, std::map<std::string,
 }
 
 struct InfoKeysHost {
-  std::vector<uint64_t> hash;
-  std::vector<int32_t> idx, id_off;
-  std::vector<uint8_t> ids, type, hflag;
-  InfoKeys view() const {
-    return InfoKeys{hash.data(), idx.data(), id_off.data(), ids.data(), type.data(), hflag.data(), (int32_t)idx.size()};
-  }
+  dqt::NameTableHost tab;
+  std::vector<uint8_t> type, hflag;
+  InfoKeys view() const { return InfoKeys{tab.view(), type.data(), hflag.data()}; }
 };
 
 // 0, or the reason the list is refused: the count, an id that is empty or holds one of ";=,\t ", an
@@ -268,8 +240,6 @@ inline const char* info_key_table_build(const std::vector<std::string>& ids, con
   const size_t K = ids.size();
   if (K < 1 || K > (size_t)INFO_MAX_KEYS || types.size() != K) return "1 to 64 keys are taken";
   *T = InfoKeysHost{};
-  T->id_off.push_back(0);
-  std::vector<std::pair<uint64_t, int32_t>> key;
   for (size_t q = 0; q < K; q++) {
     const std::string& id = ids[q];
     if (id.empty() || id.find_first_of(";=,\t ") != std::string::npos) return "an INFO key is empty or holds ';', '=', ',', a TAB or a space";
@@ -280,15 +250,8 @@ inline const char* info_key_table_build(const std::vector<std::string>& ids, con
     const int32_t ht = h == header.end() ? 0 : h->second;
     T->type.push_back((uint8_t)(types[q] != INFO_AUTO ? types[q] : ht ? ht : INFO_STRING));
     T->hflag.push_back(ht == INFO_FLAG ? 1 : 0);
-    T->ids.insert(T->ids.end(), id.begin(), id.end());
-    T->id_off.push_back((int32_t)T->ids.size());
-    key.push_back({dqv::vcf_name_hash((const uint8_t*)id.data(), (int32_t)id.size()), (int32_t)q});
   }
-  std::sort(key.begin(), key.end());
-  for (const auto& k : key) {
-    T->hash.push_back(k.first);
-    T->idx.push_back(k.second);
-  }
+  dqt::name_table_build(ids, &T->tab);
   return nullptr;
 }
 

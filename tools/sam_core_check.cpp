@@ -70,9 +70,9 @@ static int records(const char* in, const char* outp) {
   }
   put32(o, (uint32_t)H.bam.size());
   fwrite(H.bam.data(), 1, H.bam.size(), o);
-  RefTableHost RT;
-  sam_ref_table_build(H.names, &RT);
-  const RefTable R = RT.view();
+  dqt::NameTableHost RT;
+  dqt::name_table_build(H.names, &RT);
+  const dqt::NameTable R = RT.view();
   std::vector<std::pair<int64_t, int64_t>> lines;
   text_lines(t, lines);
   constexpr int GUARD = 64;

@@ -96,9 +96,9 @@ static int lines(const char* in, const char* outp) {
     return 3;
   }
   fprintf(o, "H %d %zu\n", H.G ? 1 : 0, H.contigs.size());
-  ContigTableHost CT;
-  vcf_contig_table_build(H.contigs, &CT);
-  const ContigTable C = CT.view();
+  dqt::NameTableHost CT;
+  dqt::name_table_build(H.contigs, &CT);
+  const dqt::NameTable C = CT.view();
   std::vector<std::pair<int64_t, int64_t>> ls;
   text_lines(t, ls);
   for (size_t k = 0; k < ls.size(); k++) {
@@ -169,9 +169,9 @@ static int bench(const char* in, int threads, int reps, const char* outp) {
   VcfHeader H;
   vcf_header_parse(t.data(), (int64_t)t.size(), true, &H);
   if (H.has_data && !H.has_chrom) return 3;
-  ContigTableHost CT;
-  vcf_contig_table_build(H.contigs, &CT);
-  const ContigTable C = CT.view();
+  dqt::NameTableHost CT;
+  dqt::name_table_build(H.contigs, &CT);
+  const dqt::NameTable C = CT.view();
   std::vector<std::pair<int64_t, int64_t>> all, ls;
   text_lines(t, all);
   for (const auto& l : all)

@@ -61,7 +61,7 @@ static void text_lines(const std::vector<uint8_t>& t, std::vector<std::pair<int6
 
 struct Header {
   dqv::VcfHeader H;
-  dqv::ContigTableHost CT;
+  dqt::NameTableHost CT;
   std::vector<std::string> names;
   int32_t S = 0;
 };
@@ -69,7 +69,7 @@ struct Header {
 static int read_header(const std::vector<uint8_t>& t, Header* h) {
   dqv::vcf_header_parse(t.data(), (int64_t)t.size(), true, &h->H);
   if (h->H.has_data && !h->H.has_chrom) return 3;
-  dqv::vcf_contig_table_build(h->H.contigs, &h->CT);
+  dqt::name_table_build(h->H.contigs, &h->CT);
   if (h->H.G) gt_header_samples(t.data(), (int64_t)t.size(), &h->names);
   h->S = (int32_t)h->names.size();
   return 0;
@@ -93,7 +93,7 @@ static int lines(const char* in, const char* outp) {
   }
   fprintf(o, "H %d\n", h.S);
   for (const std::string& nm : h.names) fprintf(o, "N %s\n", nm.c_str());
-  const dqv::ContigTable C = h.CT.view();
+  const dqt::NameTable C = h.CT.view();
   const int32_t S = h.S;
   std::vector<std::pair<int64_t, int64_t>> ls;
   text_lines(t, ls);
@@ -164,7 +164,7 @@ static int bench(const char* in, int threads, int reps, const char* outp) {
   if (!slurp(in, t)) return 2;
   Header h;
   if (int rc = read_header(t, &h)) return rc;
-  const dqv::ContigTable C = h.CT.view();
+  const dqt::NameTable C = h.CT.view();
   const int32_t S = h.S;
   std::vector<std::pair<int64_t, int64_t>> all;
   text_lines(t, all);

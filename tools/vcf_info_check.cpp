@@ -64,7 +64,7 @@ static void text_lines(const std::vector<uint8_t>& t, std::vector<std::pair<int6
 
 struct Setup {
   dqv::VcfHeader H;
-  dqv::ContigTableHost CT;
+  dqt::NameTableHost CT;
   InfoKeysHost KT;
   std::vector<std::string> ids;
   const char* why = nullptr;
@@ -73,7 +73,7 @@ struct Setup {
 static int setup(const std::vector<uint8_t>& t, const char* keys, Setup* S) {
   dqv::vcf_header_parse(t.data(), (int64_t)t.size(), true, &S->H);
   if (S->H.has_data && !S->H.has_chrom) return 3;
-  dqv::vcf_contig_table_build(S->H.contigs, &S->CT);
+  dqt::name_table_build(S->H.contigs, &S->CT);
   std::map<std::string, int32_t> types;
   info_header_types(t.data(), (int64_t)t.size(), &types);
   std::vector<int32_t> ty;
@@ -147,9 +147,9 @@ static int lines(const char* in, const char* keys, const char* outp) {
     return 0;
   }
   const InfoKeys T = S.KT.view();
-  const size_t K = (size_t)T.n;
+  const size_t K = (size_t)T.tab.n;
   for (size_t q = 0; q < K; q++) fprintf(o, "K %zu %s %d %d\n", q, S.ids[q].c_str(), T.type[q], T.hflag[q]);
-  const dqv::ContigTable C = S.CT.view();
+  const dqt::NameTable C = S.CT.view();
   std::vector<std::pair<int64_t, int64_t>> ls;
   text_lines(t, ls);
   for (size_t k = 0; k < ls.size(); k++) {
@@ -260,8 +260,8 @@ static int bench(const char* in, const char* keys, int threads, int reps, const 
     return 1;
   }
   const InfoKeys T = S.KT.view();
-  const size_t K = (size_t)T.n;
-  const dqv::ContigTable C = S.CT.view();
+  const size_t K = (size_t)T.tab.n;
+  const dqt::NameTable C = S.CT.view();
   std::vector<std::pair<int64_t, int64_t>> all;
   text_lines(t, all);
   std::vector<LineAt> ls;
