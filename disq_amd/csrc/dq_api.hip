@@ -229,7 +229,7 @@ struct dq_ctx {
   int64_t ncand = 0;
   // chain + inflate
   DevBuf blk_pos, blk_cs, blk_us, uoff, status, U;
-  DevBuf tails;  // inflate: the tail kernel's descriptors (16 bytes per block)
+  DevBuf tails;  // inflate: the tail descriptors and header records (INFLATE_SCRATCH_BYTES per block)
   int n_cu = 256;
   int64_t nblk = 0, ulen = 0;
   // header
@@ -790,7 +790,7 @@ static int run_pipeline(dq_ctx* ctx) {
       HIPCHK(hipMemsetAsync(tim, 0, sizeof(uint64_t) * 48 * (size_t)std::max<int64_t>(1, nblk), s));
     }
     HIPCHK(hipEventRecord(ctx->ev[5], s));
-    if ((rc = ensure_all(ctx, ctx->tails, INFLATE_TAIL_BYTES * (size_t)std::max<int64_t>(1, nblk)))) return rc;
+    if ((rc = ensure_all(ctx, ctx->tails, INFLATE_SCRATCH_BYTES * (size_t)std::max<int64_t>(1, nblk)))) return rc;
     launch_inflate3(ctx->cbuf(), ctx->blk_pos.as<int64_t>(), ctx->blk_cs.as<int32_t>(),
                     ctx->blk_us.as<int32_t>(), ctx->uoff.as<int64_t>(), nblk, ctx->U.as<uint8_t>(),
                     ctx->status.as<int32_t>(), ctx->o.verify_crc, crc_init, tim, s, nullptr, 0,
@@ -1934,7 +1934,7 @@ static int run_span(dq_ctx* ctx, const dq_traversal* tr, dq_stats* out) {
       HIPCHK(hipMemsetAsync(ctx->status.p, 0, sizeof(int32_t) * (size_t)(nblk + 1), s));
       const uint32_t* crc_init = inflate3_tables(ctx->o.device);
       if (!crc_init) RET(DQ_EDEVICE, "CRC32 table initialisation failed on this device");
-      if ((rc = ensure_all(ctx, ctx->tails, INFLATE_TAIL_BYTES * (size_t)nsel))) return rc;
+      if ((rc = ensure_all(ctx, ctx->tails, INFLATE_SCRATCH_BYTES * (size_t)nsel))) return rc;
       launch_inflate3(ctx->cbuf(), ctx->blk_pos.as<int64_t>(), ctx->blk_cs.as<int32_t>(),
                       ctx->blk_us.as<int32_t>(), ctx->uoff.as<int64_t>(), nblk, ctx->U.as<uint8_t>(),
                       ctx->status.as<int32_t>(), ctx->o.verify_crc, crc_init, nullptr, s,

@@ -12,7 +12,10 @@
 //                  waves decode the code-length sequence, one 128-bit window each: every lane
 //                  decodes the symbols at two offsets, the window's successor table is doubled by
 //                  lane shuffles, each window's exits are chained across the windows by one
-//                  thread, and runs are placed by wave scans (read_lengths).
+//                  thread, and runs are placed by wave scans (read_lengths).  The first deflate
+//                  block's dynamic header is decoded before the kernel, one lane per BGZF block
+//                  (inflate_header_kernel, round 9): the kernel loads its lengths and skips all
+//                  of the above but the header word.
 //   2. tables   -- canonical codes are assigned in parallel (wave scans of one-hot length
 //                  counters give each symbol its rank among equal lengths); 10-bit litlen / 8-bit
 //                  distance root tables of 16-bit entries that carry the decoded value (literal
@@ -46,6 +49,7 @@
 //                  multiplying with x^(8n) mod P (precomputed per slice index); compared with the
 //                  gzip trailer.
 // Output stops at ISIZE (Inflater.inflate(buf, 0, ISIZE) semantics); fewer bytes is an error.
+#include "dq_hdr_core.h"
 #include "dq_inflate_core.h"
 #include "dq_internal.h"
 
@@ -169,6 +173,34 @@ struct TailDesc {
   int32_t flag;      // 1: the tail kernel owns the rest of this block
 };
 
+// The header pre-pass (round 9, inflate_header_kernel): one lane per launched BGZF block decodes
+// the dynamic header of a deflate block serially (dq_hdr_core.h) and leaves a record the block
+// kernel (the first deflate block) and the tail kernel (the tail's first) load instead of decoding
+// the header themselves: HdrMeta i, and the 320 code lengths as nibbles in HDR_LW words at
+// lens[i * HDR_LW] (slot s in bits [4 (s & 7), +4) of word s >> 3).  The scratch buffer holds the
+// tail descriptors, the metas and the length words, in that order (INFLATE_SCRATCH_BYTES).
+// DQ_HDR_PREPASS = 0: no pre-pass, every header is decoded where it is used (round 8).
+#ifndef DQ_HDR_PREPASS
+#define DQ_HDR_PREPASS 1
+#endif
+constexpr int HDR_LW = dqh::HDR_LENS / 8;  // length words per record
+struct alignas(16) HdrMeta {
+  uint32_t info;    // kind (bits 0-1), bfinal (2), ndist (3-7), nlen (8-16), status (24-31)
+  uint32_t end;     // HDR_DYN: bit position after the header
+  uint32_t pad[2];
+};
+static_assert(sizeof(TailDesc) + sizeof(HdrMeta) + 4 * HDR_LW == INFLATE_SCRATCH_BYTES, "scratch per block");
+DQ_HD int hm_kind(uint32_t info) { return (int)(info & 3u); }
+DQ_HD int32_t hm_bfinal(uint32_t info) { return (int32_t)((info >> 2) & 1u); }
+DQ_HD int hm_ndist(uint32_t info) { return (int)((info >> 3) & 31u); }
+DQ_HD int hm_nlen(uint32_t info) { return (int)((info >> 8) & 511u); }
+DQ_HD int32_t hm_status(uint32_t info) { return (int32_t)(info >> 24); }
+// eight length nibbles -> eight length bytes
+DQ_HD uint32_t nib4(uint32_t x) {
+  x = (x | (x << 8)) & 0x00ff00ffu;
+  return (x | (x << 4)) & 0x0f0f0f0fu;
+}
+
 struct alignas(16) LdsI {
   // decode-table layout (dsym, ll_second, d_second): the second-level tables follow each root
   static constexpr int kLSUB = T_LSUB, kDROOT = T_DROOT, kDSUB = T_DSUB;
@@ -249,7 +281,8 @@ __constant__ uint32_t c_slice_shift[WG];  // x^(8 * CRC_SL * k) mod P, k = 0..WG
 __constant__ uint8_t c_clorder3[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 // misc slots
-enum { M_ERR = 0, M_SLOW = 1 /* an E_SLOW root entry in this deflate block's tables */, M_A = 4, M_LAST, M_MORE, M_MORE1,
+enum { M_ERR = 0, M_SLOW = 1 /* an E_SLOW root entry in this deflate block's tables */,
+       M_HDR = 2 /* block kernel: the pre-decoded header (HdrMeta.info) of the next deflate block, 0 none */, M_A = 4, M_LAST, M_MORE, M_MORE1,
        M_LQ0 = 15, M_LQN, M_DQ0, M_DQN, M_NEXT,
        M_LASTF, M_RCNT = 28 /* and 29: redo-list counters of even / odd rounds */,
        M_DIRTY = 30 /* and 31: a re-decoded exit changed, even / odd rounds */ };
@@ -1190,11 +1223,39 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
   // taking an HBM round trip after the header
   uint32_t warm = 0;
   if ((sflags & 16) && 128u * (uint32_t)t < (uint32_t)(mis + max(dbytes, 0))) warm = W[32 * t];
+  // The header pre-pass's record of the first deflate block (the records follow the tail
+  // descriptors; sflags bit 5: the pre-pass ran).  A decoded dynamic header: its code lengths go
+  // to L.u.d.x.h.lens here, before the barrier below, and stay there until the first turn of the
+  // loop reaches build_tables: nothing between here and there writes that union member (the
+  // stored copy writes L.out, the in-kernel header decode runs only when M_HDR is clear, `pair`
+  // is written after build_tables).  A rejected header fails the block as the in-kernel decode
+  // would; any other block type takes the in-kernel path.
+  // The loads are per thread, and M_HDR / M_A live in LDS: the record as scalar loads, or its
+  // fields held across the deflate-block loop, took SGPRs the kernel does not have (past 64
+  // spilled SGPRs a second spill VGPR, and with it 16 bytes of scratch per lane).  The address
+  // gets `+ (tid_fresh() >> 10)`, zero for every thread but opaque to the compiler, which
+  // otherwise turns the uniform address into a scalar load.
+  const bool hon = (sflags & 32) != 0;
+  uint32_t hinfo = 0;
+  if (hon) {
+    const HdrMeta* hrec = reinterpret_cast<const HdrMeta*>(tails + nblk);
+    const HdrMeta* hm = hrec + blockIdx.x + (tid_fresh() >> 10);
+    hinfo = hm->info;
+    if (hm_kind(hinfo) == dqh::HDR_DYN && t < HDR_LW) {
+      const uint32_t w = reinterpret_cast<const uint32_t*>(hrec + nblk)[(int64_t)blockIdx.x * HDR_LW + t];
+      uint32_t* l8 = reinterpret_cast<uint32_t*>(L.u.d.x.h.lens);
+      l8[2 * t] = nib4(w & 0xffffu);
+      l8[2 * t + 1] = nib4(w >> 16);
+    }
+    if (t == M_A) L.misc[M_A] = (int32_t)hm->end;
+    if (t == M_HDR) L.misc[M_HDR] = hm_kind(hinfo) == dqh::HDR_DYN ? (int32_t)hinfo : 0;
+  }
   for (int i = t; i < 2048; i += WG) L.bm[i] = 0;
-  if (t < 32) L.misc[t] = 0;
+  if (t < 32 && !(hon && (t == M_A || t == M_HDR))) L.misc[t] = 0;
   if (t == 0) {
     if (isize < 0 || isize > 65536) L.misc[M_ERR] = ST_ISIZE;
     else if (dbytes < 0) L.misc[M_ERR] = ST_OVERREAD;
+    else if (isize > 0 && hm_kind(hinfo) == dqh::HDR_ERR) L.misc[M_ERR] = hm_status(hinfo);
   }
   asm volatile("" ::"v"(warm));
   __syncthreads();
@@ -1211,8 +1272,10 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
                                      // previous deflate block's flag precedes the emit barrier
     const uint32_t clpos = pos + 17;
     const uint32_t hbase = clpos >> 5;
-    const uint32_t hw = t < HB_WORDS ? W[hbase + t] : 0u;
-    const uint32_t hcl = t < 19 ? peek_bits(W, clpos + 3 * t, 3) : 0u;
+    // (a header the pre-pass decoded needs neither the staged words nor the code-length code)
+    const bool hpre = L.misc[M_HDR] != 0;
+    const uint32_t hw = !hpre && t < HB_WORDS ? W[hbase + t] : 0u;
+    const uint32_t hcl = !hpre && t < 19 ? peek_bits(W, clpos + 3 * t, 3) : 0u;
     const uint32_t h = peek_bits(W, pos, 17);
     const int32_t bfinal = (int32_t)(h & 1), btype = (int32_t)((h >> 1) & 3);
     const int32_t herr = pos + 3 > endbits ? ST_OVERREAD : btype == 3 ? ST_BAD_BLOCKTYPE : 0;
@@ -1249,6 +1312,11 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       for (int i = t; i < 320; i += WG) L.u.d.x.h.lens[i] = fixed_len(i);
       if (t == 0) L.misc[M_A] = (int32_t)(pos + 3);
       __syncthreads();
+    } else if (hpre) {
+      // the first deflate block's header was decoded by the pre-pass: its lengths and M_A are in
+      // LDS (no staging, no code-length table, no read_lengths; h gives nlen, ndist and bfinal)
+      __syncthreads();
+      if (t == 0) L.misc[M_HDR] = 0;  // only the first deflate block's header is pre-decoded
     } else {
       const int ncode = (int)((h >> 13) & 15) + 4;
       for (int i = t; i < 320; i += WG) L.u.d.x.h.lens[i] = 0;
@@ -2027,6 +2095,94 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     for (int i = 0; i < 7; i++) tim[(int64_t)blockIdx.x * TIM_W + 24 + i] = (uint64_t)L.misc[21 + i];
 }
 
+// ================================================================ the header pre-pass
+// One lane per launched BGZF block, one wave per workgroup.  Lane i decodes the header of block
+// sel[i] (or i) at the start of its deflate data -- or, TAIL, at tails[i].pos where tails[i].flag
+// is set -- with dq_hdr_core.h's serial decoder, and writes record i (HdrMeta, HDR_LW length
+// words).  Per lane in LDS: the 128 one-byte entries of the code-length code's decode table
+// (entry k at k * 64 + lane) and the HDR_LW length words (word w at w * HP_LS + lane; HP_LS odd, so
+// the write-out's reads, 64 consecutive global words = 1.6 records per instruction, spread over
+// the banks).  The lengths leave the wave as HDR_LW stores of 64 consecutive words: a lane's own
+// 160 bytes written from its registers would be 64 scattered lines per store.
+// The reads: 32-bit words between the word of the header's first bit and HDR_WORDS - 1 words after
+// it, the range the block and tail kernels stage (C's pad covers it at the end of the file).
+constexpr int HP_LS = 65;
+struct HpSrc {
+  const uint32_t* __restrict__ W;
+  uint32_t last;  // the last word the header may read
+  DQ_AI uint32_t word(uint32_t i) const {
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(W) + (min(i, last) << 2));
+  }
+};
+struct HpTbl {
+  uint8_t* t;  // + lane
+  DQ_AI void set(uint32_t k, uint32_t v) { t[k * 64] = (uint8_t)v; }
+  DQ_AI uint32_t get(uint32_t k) const { return t[k * 64]; }
+};
+struct HpSink {  // slots come in increasing order: a word is stored when the next one begins
+  uint32_t* w;   // + lane
+  uint32_t cur, acc;
+  DQ_AI void put(uint32_t i, uint32_t v) {
+    if ((i >> 3) != cur) {
+      flush();
+      cur = i >> 3;
+      acc = 0;
+    }
+    acc |= v << (4 * (i & 7));
+  }
+  DQ_AI void flush() {
+    if (acc) w[cur * HP_LS] = acc;
+  }
+};
+
+template <bool TAIL>
+__global__ __launch_bounds__(64) void inflate_header_kernel(
+    const uint8_t* __restrict__ C, const int64_t* __restrict__ blk_pos,
+    const int32_t* __restrict__ blk_csize, int64_t ngrid, const int32_t* __restrict__ sel,
+    const TailDesc* __restrict__ tails, HdrMeta* __restrict__ hdr) {
+  __shared__ uint8_t clt[128 * 64];
+  __shared__ uint32_t lw[HDR_LW * HP_LS];
+  const int lane = (int)threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + lane;
+  bool act = i < ngrid;
+  uint32_t pos = 0;
+  if (TAIL && act) {
+    const TailDesc td = tails[i];
+    act = td.flag == 1;
+    pos = (uint32_t)td.pos;
+  }
+  for (int w = 0; w < HDR_LW; w++) lw[w * HP_LS + lane] = 0;
+  dqh::HdrInfo R = {dqh::HDR_NONE, 0, 0, 0, 0, 0};
+  if (act) {
+    const int64_t b = sel ? (int64_t)sel[i] : i;
+    const uint8_t* dp = C + blk_pos[b] + 18;  // as the block kernel: bit positions from the
+    const int mis = (int)(reinterpret_cast<uintptr_t>(dp) & 15);  // 16-byte aligned base
+    const uint32_t a0 = 8u * (uint32_t)mis;
+    const uint32_t endbits = a0 + 8u * (uint32_t)max(blk_csize[b] - 26, 0);
+    if (!TAIL) pos = a0;
+    const HpSrc S{reinterpret_cast<const uint32_t*>(dp - mis), (pos >> 5) + dqh::HDR_WORDS - 1};
+    HpTbl T{clt + lane};
+    HpSink K{lw + lane, 0, 0};
+    R = dqh::hdr_decode(S, T, K, pos, endbits);
+    K.flush();
+    HdrMeta m;
+    m.info = (uint32_t)R.kind | (uint32_t)R.bfinal << 2 | (uint32_t)(R.ndist & 31) << 3 |
+             (uint32_t)(R.nlen & 511) << 8 | (uint32_t)R.status << 24;
+    m.end = R.end;
+    m.pad[0] = m.pad[1] = 0;
+    hdr[i] = m;
+  }
+  // the length words of this wave's records: HDR_LW * 64 consecutive global words (records that
+  // hold no decoded header are not written)
+  __syncthreads();
+  const uint64_t dyn = __ballot(R.kind == dqh::HDR_DYN);
+  uint32_t* out = reinterpret_cast<uint32_t*>(hdr + ngrid) + i0 * HDR_LW;
+  for (int k = 0; k < HDR_LW; k++) {
+    const int g = 64 * k + lane, r = g / HDR_LW, w = g - r * HDR_LW;
+    if ((dyn >> r) & 1) out[g] = lw[w * HP_LS + r];
+  }
+}
+
 // ================================================================ the tail kernel
 // Per-wave LDS of inflate_tail_kernel (~13 KB: four tails per workgroup, three workgroups per CU).
 struct alignas(16) LdsW {
@@ -2341,6 +2497,23 @@ __global__ __launch_bounds__(64 * TW, 4) void inflate_tail_kernel(
   }
   for (int i = lane; i < TOUT / 32; i += 64) L.bm[i] = 0;
   if (lane < 8) L.misc[lane] = 0;
+  // the header pre-pass's record of the tail's first deflate block (as the block kernel: a decoded
+  // dynamic header's lengths go to LDS here, a rejected one fails the block)
+  uint32_t hinfo = 0, hend = 0;
+  if (sflags & 32) {  // the records follow the tail descriptors
+    const HdrMeta* hdr = reinterpret_cast<const HdrMeta*>(tails + ngrid);
+    const HdrMeta hm = hdr[gi];
+    hinfo = hm.info;
+    hend = hm.end;
+    if (hm_kind(hinfo) == dqh::HDR_DYN && lane < HDR_LW) {
+      const uint32_t w = reinterpret_cast<const uint32_t*>(hdr + ngrid)[gi * HDR_LW + lane];
+      uint32_t* l8 = reinterpret_cast<uint32_t*>(L.u.d.x.h.lens);
+      l8[2 * lane] = nib4(w & 0xffffu);
+      l8[2 * lane + 1] = nib4(w >> 16);
+    }
+    if (hm_kind(hinfo) == dqh::HDR_ERR && lane == 0) L.misc[M_ERR] = hm_status(hinfo);
+  }
+  const bool hpre = hm_kind(hinfo) == dqh::HDR_DYN;
   __builtin_amdgcn_wave_barrier();
   int32_t produced = p0;
   uint32_t pos = (uint32_t)td.pos;
@@ -2355,84 +2528,94 @@ __global__ __launch_bounds__(64 * TW, 4) void inflate_tail_kernel(
   };
   while (L.misc[M_ERR] == 0 && produced < isize) {
     // ---- header (as the block kernel: every lane reads it, the branches are uniform)
-    const uint32_t clpos = pos + 17;
-    const uint32_t hbase = clpos >> 5;
-#if DQ_TAIL_HDR1
-    // every load of the header in one round trip: the block header, a dynamic header's staged
-    // words and its code-length code lengths (HCLEN is not known yet: all 19 are loaded; a stored
-    // or fixed block's over-read stays inside the 4096 zero bytes that follow C)
-    constexpr int HWN = (HB_WORDS + 63) / 64;
-    uint32_t hw[HWN];
-#pragma unroll
-    for (int j = 0; j < HWN; j++) hw[j] = lane + 64 * j < HB_WORDS ? W[hbase + lane + 64 * j] : 0u;
-    const uint32_t clv = lane < 19 ? peek_bits(W, clpos + 3 * (uint32_t)lane, 3) : 0u;
-#endif
-    const uint32_t h = peek_bits(W, pos, 17);
-    const int32_t bfinal = (int32_t)(h & 1), btype = (int32_t)((h >> 1) & 3);
-    const int32_t herr = pos + 3 > endbits ? ST_OVERREAD : btype == 3 ? ST_BAD_BLOCKTYPE : 0;
-    if (herr) {
-      set_err(L, herr);
-      break;
-    }
-    if (btype == 0) {  // stored block: copy
-      const uint32_t q = (pos + 3 + 7) & ~7u;
-      const uint8_t* bp = reinterpret_cast<const uint8_t*>(W) + q / 8;
-      const uint32_t len = bp[0] | ((uint32_t)bp[1] << 8), nl = bp[2] | ((uint32_t)bp[3] << 8);
-      const int32_t serr = (len ^ 0xffffu) != nl ? ST_BAD_STORED : q + 32 + 8 * len > endbits ? ST_OVERREAD : 0;
-      if (serr) {
-        set_err(L, serr);
-        break;
-      }
-      const int32_t n = min((int32_t)len, isize - produced);
-      if (produced + n - p0 > TOUT) {
-        set_err(L, ST_SHORT);
-        break;
-      }
-      for (int i = lane; i < n; i += 64) L.out[sh + produced - p0 + i] = bp[4 + i];
-      produced += n;
-      pos = q + 32 + 8 * len;
-      __builtin_amdgcn_wave_barrier();
-      if (bfinal) break;
-      continue;
-    }
-    const int nlen = btype == 1 ? 288 : (int)((h >> 3) & 31) + 257;
-    const int ndist = btype == 1 ? 32 : (int)((h >> 8) & 31) + 1;
-    if (btype == 2 && (nlen > 286 || ndist > 30)) {
-      set_err(L, ST_BAD_TABLE);
-      break;
-    }
+    int nlen, ndist;
+    int32_t bfinal;
     uint32_t a;
-    if (btype == 1) {
-      for (int i = lane; i < 320; i += 64) L.u.d.x.h.lens[i] = fixed_len(i);
-      a = pos + 3;
+    if (hpre && pos == (uint32_t)td.pos) {  // pre-decoded: the lengths are in LDS
+      nlen = hm_nlen(hinfo);
+      ndist = hm_ndist(hinfo);
+      bfinal = hm_bfinal(hinfo);
+      a = hend;
     } else {
-      const int ncode = (int)((h >> 13) & 15) + 4;
-      for (int i = lane; i < 320; i += 64) L.u.d.x.h.lens[i] = 0;
+      const uint32_t clpos = pos + 17;
+      const uint32_t hbase = clpos >> 5;
 #if DQ_TAIL_HDR1
+      // every load of the header in one round trip: the block header, a dynamic header's staged
+      // words and its code-length code lengths (HCLEN is not known yet: all 19 are loaded; a stored
+      // or fixed block's over-read stays inside the 4096 zero bytes that follow C)
+      constexpr int HWN = (HB_WORDS + 63) / 64;
+      uint32_t hw[HWN];
 #pragma unroll
-      for (int j = 0; j < HWN; j++)
-        if (lane + 64 * j < HB_WORDS) reinterpret_cast<uint32_t*>(L.u.d.T)[lane + 64 * j] = hw[j];
-      if (lane < 19) L.u.d.x.h.clen[c_clorder3[lane]] = lane < ncode ? (uint8_t)clv : 0;
-#else
-      for (int i = lane; i < HB_WORDS; i += 64) reinterpret_cast<uint32_t*>(L.u.d.T)[i] = W[hbase + i];
-      if (lane < 19)
-        L.u.d.x.h.clen[c_clorder3[lane]] = lane < ncode ? (uint8_t)peek_bits(W, clpos + 3 * lane, 3) : 0;
+      for (int j = 0; j < HWN; j++) hw[j] = lane + 64 * j < HB_WORDS ? W[hbase + lane + 64 * j] : 0u;
+      const uint32_t clv = lane < 19 ? peek_bits(W, clpos + 3 * (uint32_t)lane, 3) : 0u;
 #endif
-      __builtin_amdgcn_wave_barrier();
-      bool ok = true;
-      L.u.d.x.h.clt[lane] = clt_entry(L.u.d.x.h.clen, lane, &ok);
-      L.u.d.x.h.clt[lane + 64] = clt_entry(L.u.d.x.h.clen, lane + 64, &ok);
-      if (__any(!ok)) {
+      const uint32_t h = peek_bits(W, pos, 17);
+      bfinal = (int32_t)(h & 1);
+      const int32_t btype = (int32_t)((h >> 1) & 3);
+      const int32_t herr = pos + 3 > endbits ? ST_OVERREAD : btype == 3 ? ST_BAD_BLOCKTYPE : 0;
+      if (herr) {
+        set_err(L, herr);
+        break;
+      }
+      if (btype == 0) {  // stored block: copy
+        const uint32_t q = (pos + 3 + 7) & ~7u;
+        const uint8_t* bp = reinterpret_cast<const uint8_t*>(W) + q / 8;
+        const uint32_t len = bp[0] | ((uint32_t)bp[1] << 8), nl = bp[2] | ((uint32_t)bp[3] << 8);
+        const int32_t serr = (len ^ 0xffffu) != nl ? ST_BAD_STORED : q + 32 + 8 * len > endbits ? ST_OVERREAD : 0;
+        if (serr) {
+          set_err(L, serr);
+          break;
+        }
+        const int32_t n = min((int32_t)len, isize - produced);
+        if (produced + n - p0 > TOUT) {
+          set_err(L, ST_SHORT);
+          break;
+        }
+        for (int i = lane; i < n; i += 64) L.out[sh + produced - p0 + i] = bp[4 + i];
+        produced += n;
+        pos = q + 32 + 8 * len;
+        __builtin_amdgcn_wave_barrier();
+        if (bfinal) break;
+        continue;
+      }
+      nlen = btype == 1 ? 288 : (int)((h >> 3) & 31) + 257;
+      ndist = btype == 1 ? 32 : (int)((h >> 8) & 31) + 1;
+      if (btype == 2 && (nlen > 286 || ndist > 30)) {
         set_err(L, ST_BAD_TABLE);
         break;
       }
-      __builtin_amdgcn_wave_barrier();
-      a = read_lengths_wave(L, clpos + 3 * (uint32_t)ncode, nlen, ndist, endbits, hbase);
-      __builtin_amdgcn_wave_barrier();
-      if (L.misc[M_ERR]) break;
-      if (L.u.d.x.h.lens[256] == 0) {  // an EOB code is required
-        set_err(L, ST_BAD_TABLE);
-        break;
+      if (btype == 1) {
+        for (int i = lane; i < 320; i += 64) L.u.d.x.h.lens[i] = fixed_len(i);
+        a = pos + 3;
+      } else {
+        const int ncode = (int)((h >> 13) & 15) + 4;
+        for (int i = lane; i < 320; i += 64) L.u.d.x.h.lens[i] = 0;
+#if DQ_TAIL_HDR1
+#pragma unroll
+        for (int j = 0; j < HWN; j++)
+          if (lane + 64 * j < HB_WORDS) reinterpret_cast<uint32_t*>(L.u.d.T)[lane + 64 * j] = hw[j];
+        if (lane < 19) L.u.d.x.h.clen[c_clorder3[lane]] = lane < ncode ? (uint8_t)clv : 0;
+#else
+        for (int i = lane; i < HB_WORDS; i += 64) reinterpret_cast<uint32_t*>(L.u.d.T)[i] = W[hbase + i];
+        if (lane < 19)
+          L.u.d.x.h.clen[c_clorder3[lane]] = lane < ncode ? (uint8_t)peek_bits(W, clpos + 3 * lane, 3) : 0;
+#endif
+        __builtin_amdgcn_wave_barrier();
+        bool ok = true;
+        L.u.d.x.h.clt[lane] = clt_entry(L.u.d.x.h.clen, lane, &ok);
+        L.u.d.x.h.clt[lane + 64] = clt_entry(L.u.d.x.h.clen, lane + 64, &ok);
+        if (__any(!ok)) {
+          set_err(L, ST_BAD_TABLE);
+          break;
+        }
+        __builtin_amdgcn_wave_barrier();
+        a = read_lengths_wave(L, clpos + 3 * (uint32_t)ncode, nlen, ndist, endbits, hbase);
+        __builtin_amdgcn_wave_barrier();
+        if (L.misc[M_ERR]) break;
+        if (L.u.d.x.h.lens[256] == 0) {  // an EOB code is required
+          set_err(L, ST_BAD_TABLE);
+          break;
+        }
       }
     }
     tick(0);
@@ -2842,7 +3025,7 @@ const uint32_t* inflate3_tables(int device) {
 void launch_inflate3(const uint8_t* C, const int64_t* blk_pos, const int32_t* blk_csize,
                      const int32_t* blk_usize, const int64_t* uoff, int64_t nblk, uint8_t* U,
                      int32_t* status, int32_t verify_crc, const uint32_t* crc_init, uint64_t* tim,
-                     hipStream_t s, const int32_t* sel, int64_t nsel, void* tails_buf) {
+                     hipStream_t s, const int32_t* sel, int64_t nsel, void* scratch) {
   if (nblk <= 0) return;
   const int64_t ngrid = sel ? nsel : nblk;
   if (ngrid <= 0) return;
@@ -2866,28 +3049,40 @@ void launch_inflate3(const uint8_t* C, const int64_t* blk_pos, const int32_t* bl
   constexpr unsigned ldspad = 0u;
   constexpr bool tail_on = true;
 #endif
-  TailDesc* td = tail_on ? static_cast<TailDesc*>(tails_buf) : nullptr;
+  // the scratch: ngrid tail descriptors, ngrid header metas, ngrid * HDR_LW length words
+  TailDesc* td = tail_on ? static_cast<TailDesc*>(scratch) : nullptr;
+  HdrMeta* hm = DQ_HDR_PREPASS && td ? reinterpret_cast<HdrMeta*>(td + ngrid) : nullptr;
+  const uint32_t kflags = sflags | (hm ? 32u : 0u);  // bit 5: the kernels read the header records
   if (td) (void)hipMemsetAsync(td, 0, sizeof(TailDesc) * (size_t)ngrid, s);
+  const dim3 hgrid((unsigned)((ngrid + 63) / 64));
+  // the headers of the first deflate blocks, one lane per block
+  if (hm)
+    hipLaunchKernelGGL((inflate_header_kernel<false>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid, sel,
+                       (const TailDesc*)nullptr, hm);
 #define DQ_LAUNCH(TM, NBT, GT)                                                                  \
   hipLaunchKernelGGL((inflate_block_kernel<TM, NBT, GT>), dim3((unsigned)ngrid), dim3(WG), ldspad, s, C, \
                      blk_pos, blk_csize, blk_usize, uoff, ngrid, U, status, verify_crc, crc_init, tim, ov, \
-                     sflags, sel, td)
+                     kflags, sel, td)
   // NB = 4 chunks of G = 1 byte per thread: (1, 4) measures the same, (2, 1) slower (round 5)
   if (tim)
     DQ_LAUNCH(true, DQ_RES_NB, DQ_RES_G);
   else
     DQ_LAUNCH(false, DQ_RES_NB, DQ_RES_G);
 #undef DQ_LAUNCH
+  // the headers of the deferred tails, into the records the block kernel has consumed
+  if (td && hm)
+    hipLaunchKernelGGL((inflate_header_kernel<true>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid, sel,
+                       (const TailDesc*)td, hm);
   // DQ_TIMING: the block kernel's phases in tim[0, TIM_W ngrid), the tail kernel's in the 16 ngrid
   // words after them (16 per tail; dq_api allocates TIM_W + 16 per block)
   if (td && tim)
     hipLaunchKernelGGL((inflate_tail_kernel<true>), dim3((unsigned)((ngrid + TW - 1) / TW)), dim3(64 * TW), 0, s,
                        C, blk_pos, blk_csize, blk_usize, uoff, ngrid, U, status, verify_crc, crc_init,
-                       ov == OV_DEFAULT ? (uint32_t)DQ_TAIL_OV : ov, sflags, sel, td, tim + TIM_W * ngrid);  // 16 words per tail
+                       ov == OV_DEFAULT ? (uint32_t)DQ_TAIL_OV : ov, kflags, sel, td, tim + TIM_W * ngrid);  // 16 words per tail
   else if (td)
     hipLaunchKernelGGL((inflate_tail_kernel<false>), dim3((unsigned)((ngrid + TW - 1) / TW)), dim3(64 * TW), 0, s,
                        C, blk_pos, blk_csize, blk_usize, uoff, ngrid, U, status, verify_crc, crc_init,
-                       ov == OV_DEFAULT ? (uint32_t)DQ_TAIL_OV : ov, sflags, sel, td, nullptr);
+                       ov == OV_DEFAULT ? (uint32_t)DQ_TAIL_OV : ov, kflags, sel, td, nullptr);
 }
 
 }  // namespace dq

@@ -1,0 +1,81 @@
+// hdr_core_check -- the serial DEFLATE block-header decoder of disq_amd/csrc/dq_hdr_core.h
+// (hdr_decode, what one lane of inflate_header_kernel runs) on the CPU, for
+// tests/test_hdr_core_cpu.py:
+//   hdr_core_check CASES     one line per case: kind status nlen ndist bfinal end, then the 320 code
+//                            lengths as hex digits (litlen at [0, 288), distance at [288, 320))
+// CASES (binary, little endian): per case three u32 -- the byte count n, the header's bit position
+// and the bit position of the end of the member's deflate data -- and the n bytes.  As the kernels'
+// compressed buffer, the bytes are followed by a zero pad (4096 bytes, allocated exactly: a read
+// past it is a sanitizer error), and the reader clamps its word index to HDR_WORDS words from the
+// header's first word.
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "dq_hdr_core.h"
+
+namespace {
+
+constexpr size_t PAD = 4096;
+
+struct Src {
+  const uint8_t* p;
+  uint32_t base;
+  uint32_t word(uint32_t i) const {
+    uint32_t v;
+    memcpy(&v, p + 4 * (size_t)std::min(i, base + dqh::HDR_WORDS - 1), 4);
+    return v;
+  }
+};
+struct Tbl {
+  uint8_t t[128];
+  int writes = 0;
+  void set(uint32_t k, uint32_t v) {
+    t[k] = (uint8_t)v;
+    writes++;
+  }
+  uint32_t get(uint32_t k) const { return t[k]; }
+};
+struct Sink {
+  uint8_t lens[dqh::HDR_LENS];
+  int64_t last = -1;
+  bool ordered = true;
+  void put(uint32_t i, uint32_t v) {
+    ordered = ordered && (int64_t)i > last;  // the device sink relies on increasing slots
+    last = i;
+    lens[i] = (uint8_t)v;
+  }
+};
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc != 2) {
+    fprintf(stderr, "usage: hdr_core_check CASES\n");
+    return 2;
+  }
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  uint32_t hd[3];
+  while (fread(hd, 4, 3, f) == 3) {
+    const uint32_t n = hd[0], pos = hd[1], endbits = hd[2];
+    // a heap block of exactly the bytes and the pad
+    std::vector<uint8_t> buf((size_t)n + PAD, 0);
+    if (n && fread(buf.data(), 1, n, f) != n) return 2;
+    if ((uint64_t)(pos >> 5) * 4 + dqh::HDR_WORDS * 4 > buf.size()) return 3;  // the case's own bound
+    Src S{buf.data(), pos >> 5};
+    Tbl T;
+    memset(T.t, 0, sizeof T.t);
+    Sink K;
+    memset(K.lens, 0, sizeof K.lens);
+    const dqh::HdrInfo R = dqh::hdr_decode(S, T, K, pos, endbits);
+    if (!K.ordered || T.writes > 128) return 4;
+    printf("%d %d %d %d %d %u ", R.kind, R.status, R.nlen, R.ndist, R.bfinal, R.end);
+    for (int i = 0; i < dqh::HDR_LENS; i++) putchar("0123456789abcdef"[K.lens[i] & 15]);
+    putchar('\n');
+  }
+  fclose(f);
+  return 0;
+}
