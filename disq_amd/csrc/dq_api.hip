@@ -786,8 +786,8 @@ static int run_pipeline(dq_ctx* ctx) {
     static const bool timing = getenv("DQ_TIMING") != nullptr;
     uint64_t* tim = nullptr;
     if (timing) {
-      HIPCHK(hipMalloc(&tim, sizeof(uint64_t) * 48 * (size_t)std::max<int64_t>(1, nblk)));
-      HIPCHK(hipMemsetAsync(tim, 0, sizeof(uint64_t) * 48 * (size_t)std::max<int64_t>(1, nblk), s));
+      HIPCHK(hipMalloc(&tim, sizeof(uint64_t) * INFLATE_TIM_WORDS * (size_t)std::max<int64_t>(1, nblk)));
+      HIPCHK(hipMemsetAsync(tim, 0, sizeof(uint64_t) * INFLATE_TIM_WORDS * (size_t)std::max<int64_t>(1, nblk), s));
     }
     HIPCHK(hipEventRecord(ctx->ev[5], s));
     if ((rc = ensure_all(ctx, ctx->tails, INFLATE_SCRATCH_BYTES * (size_t)std::max<int64_t>(1, nblk)))) return rc;
@@ -797,7 +797,8 @@ static int run_pipeline(dq_ctx* ctx) {
                     ctx->tails.p);
     HIPCHK(hipEventRecord(ctx->ev[6], s));
     if (timing) {
-      std::vector<uint64_t> h(48 * (size_t)nblk);  // 32 words per block (TIM_W), 16 per tail
+      // 32 words per block (TIM_W), 16 per tail, then 8 per wave (64 blocks) and pre-pass launch
+      std::vector<uint64_t> h(INFLATE_TIM_WORDS * (size_t)nblk);
       HIPCHK(hipMemcpyAsync(h.data(), tim, 8 * h.size(), hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       (void)hipFree(tim);
@@ -836,6 +837,17 @@ static int run_pipeline(dq_ctx* ctx) {
         fprintf(stderr, "[dq] tail rows per tail %.1f, jump rounds per row %.2f, rows with in-row chains %.1f %%, "
                 "round cycles per tail %.0f\n", ta[9] / ta[3], ta[10] / std::max(1.0, ta[9]),
                 100.0 * ta[11] / std::max(1.0, ta[9]), ta[12] / ta[3]);
+      // the header pre-pass: lane 0 of each wave, the first blocks' launch and the tails'
+      for (int tl = 0; tl < 2; tl++) {
+        double hp[8] = {0};
+        const int64_t nw = (nblk + 63) / 64;
+        for (int64_t w = 0; w < nw; w++)
+          for (int k = 0; k < 8; k++) hp[k] += (double)h[48 * (size_t)nblk + 8 * (size_t)(2 * w + tl) + k];
+        if (hp[5] > 0)
+          fprintf(stderr, "[dq] header pre-pass (%s): %.0f waves, cycles per wave (lane 0): loads=%.0f "
+                  "cl_code=%.0f cl_table=%.0f lengths=%.0f write=%.0f\n", tl ? "tails" : "first blocks",
+                  hp[5], hp[0] / hp[5], hp[1] / hp[5], hp[2] / hp[5], hp[3] / hp[5], hp[4] / hp[5]);
+      }
     }
   }
   dbg(s, "inflate", nblk, ulen);

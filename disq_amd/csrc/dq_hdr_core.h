@@ -8,13 +8,30 @@
 // global memory + LDS:
 //   Src:  uint32_t word(uint32_t i)        32-bit word i of the compressed data (the source clamps
 //                                          i to what it may read: hdr_decode never reads more than
-//                                          HDR_WORDS words from the word of the header's first bit)
+//                                          HDR_WORDS words from the word of the header's first bit).
+//                                          The words are asked for in increasing order, the first
+//                                          one being the word of the header's first bit, and each
+//                                          once: a source may read ahead and keep state
+//         void ahead(uint32_t i)           before every length symbol, outside any branch on the
+//                                          header's bits: word i is the next one to be asked for,
+//                                          at most one word is asked for before the next call, and
+//                                          at most six before the first.  A source that reads ahead
+//                                          moves its window here (all lanes of a wave at once)
 //   Tbl:  void set(uint32_t k, uint32_t v) entry k < 128 of the code-length code's 7-bit decode
 //         uint32_t get(uint32_t k)         table (sym << 3 | len, one byte; 0 = no code)
-//   Sink: void put(uint32_t i, uint32_t v) code length v (1..15) of symbol slot i, the layout the
-//                                          kernels' build_tables reads: litlen at [0, 288), distance
-//                                          at [288, 320); called in increasing i, zero lengths are
-//                                          not put (the sink starts zero filled)
+//   Sink: void run(uint32_t i, uint32_t n, uint32_t v)
+//                                          the n (1..6) symbol slots from i on have the code length
+//                                          v (1..15); slots in the layout the kernels' build_tables
+//                                          reads: litlen at [0, 288), distance at [288, 320), a run
+//                                          lies in one of them.  Called with increasing i; zero
+//                                          lengths are not sent (the sink starts zero filled).
+//                                          Summed per v and alphabet, n gives the numbers of codes
+//                                          of each length (at most 286 and 30): what a canonical
+//                                          code is built from
+//         void mark(int k)                 a phase of the decode ends (k = 0 the code-length code's
+//                                          lengths are read, 1 its table is filled, 2 the length
+//                                          loop is over; not called on every early return): for a
+//                                          caller that times the phases, empty otherwise
 #pragma once
 #include <stdint.h>
 
@@ -52,13 +69,14 @@ template <class Src>
 struct Bits {
   uint64_t bb;
   uint32_t bc, wp;
-  DQH_INLINE void init(const Src& S, uint32_t pos) {
+  DQH_INLINE void init(Src& S, uint32_t pos) {
     const uint32_t wi = pos >> 5, sh = pos & 31;
-    bb = (((uint64_t)S.word(wi + 1) << 32) | S.word(wi)) >> sh;
+    const uint32_t w0 = S.word(wi);
+    bb = (((uint64_t)S.word(wi + 1) << 32) | w0) >> sh;
     bc = 64 - sh;
     wp = wi + 2;
   }
-  DQH_INLINE void fill(const Src& S) {
+  DQH_INLINE void fill(Src& S) {
     if (bc <= 32) {
       bb |= (uint64_t)S.word(wp) << bc;
       bc += 32;
@@ -78,8 +96,13 @@ struct Bits {
 // stored lengths each), and the reader advances at most 17 + 57 + 316 * 14 bits: corrupt input can
 // neither spin the caller nor move it past HDR_WORDS words.
 template <class Src, class Tbl, class Sink>
-DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint32_t endbits) {
-  constexpr uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+DQH_INLINE HdrInfo hdr_decode(Src& S, Tbl& T, Sink& K, uint32_t pos, uint32_t endbits) {
+  // the order the code-length code's lengths come in (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12,
+  // 3, 13, 2, 14, 1, 15), five bits each: twelve in ord_lo, seven in ord_hi (an array of bytes is a
+  // load from constant memory per length on the device)
+  constexpr uint64_t ord_lo = 16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 |
+                              9ull << 30 | 6ull << 35 | 10ull << 40 | 5ull << 45 | 11ull << 50 | 4ull << 55;
+  constexpr uint64_t ord_hi = 12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30;
   HdrInfo R = {HDR_NONE, 0, 0, 0, 0, pos};
   if (pos + 3 > endbits) return R;  // the caller reports it (with the block types it handles)
   Bits<Src> B;
@@ -105,7 +128,8 @@ DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint3
     B.fill(S);
     const uint32_t v = i < ncode ? B.peek() & 7 : 0;
     B.skip(i < ncode ? 3 : 0);
-    cl |= (uint64_t)v << (3 * order[i]);
+    const uint32_t sym = (uint32_t)(i < 12 ? ord_lo >> (5 * i) : ord_hi >> (5 * (i - 12))) & 31;
+    cl |= (uint64_t)v << (3 * sym);
     cnt += 1ull << (8 * v);
   }
   // complete and not over-subscribed (as the kernels' clt_entry); the first code of each length
@@ -124,6 +148,7 @@ DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint3
     }
     if (!ok || left != 0) return R;
   }
+  K.mark(0);
   // the 7-bit decode table: every entry is written exactly once (the code is complete)
   for (int s = 0; s < 19; s++) {
     const uint32_t l = (uint32_t)(cl >> (3 * s)) & 7;
@@ -134,6 +159,7 @@ DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint3
     for (uint32_t i = 0; i < l; i++) r |= ((c >> i) & 1u) << (l - 1 - i);
     for (uint32_t k = r & 127; k < 128; k += 1u << l) T.set(k, (uint32_t)s << 3 | l);
   }
+  K.mark(1);
   // the nlen + ndist lengths; runs (16/17/18) cross from the litlen into the distance alphabet
   const int total = R.nlen + R.ndist;
   int have = 0, prev = -1;
@@ -143,6 +169,7 @@ DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint3
       R.status = HDR_OVERREAD;
       return R;
     }
+    S.ahead(B.wp);
     B.fill(S);
     const uint32_t v = B.peek();
     const uint32_t e = T.get(v & 127);
@@ -155,14 +182,17 @@ DQH_INLINE HdrInfo hdr_decode(const Src& S, Tbl& T, Sink& K, uint32_t pos, uint3
     const int val = sy < 16 ? (int)sy : sy == 16 ? prev : 0;
     if (val < 0) return R;              // a repeat with no length before it
     if (have + rep > total) return R;   // a run past HLIT + HDIST
-    if (val != 0)
-      for (int i = have; i < have + rep; i++) {  // rep <= 6 here
-        K.put((uint32_t)(i < R.nlen ? i : 288 + i - R.nlen), (uint32_t)val);
-        eob = eob || i == 256;
-      }
+    if (val != 0) {  // rep <= 6 here: the run's litlen part, or all of it; the rest of a run that
+                     // crosses into the distance alphabet
+      const int nl = have >= R.nlen ? 0 : have + rep <= R.nlen ? rep : R.nlen - have;
+      K.run((uint32_t)(nl ? have : 288 + have - R.nlen), (uint32_t)(nl ? nl : rep), (uint32_t)val);
+      if (nl != 0 && nl != rep) K.run(288u, (uint32_t)(rep - nl), (uint32_t)val);
+      eob = eob || (have <= 256 && have + rep > 256);
+    }
     have += rep;
     prev = val;
   }
+  K.mark(2);
   if (have < total) return R;
   R.end = B.pos();
   if (R.end > endbits) {

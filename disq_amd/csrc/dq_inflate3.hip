@@ -177,8 +177,11 @@ struct TailDesc {
 // the dynamic header of a deflate block serially (dq_hdr_core.h) and leaves a record the block
 // kernel (the first deflate block) and the tail kernel (the tail's first) load instead of decoding
 // the header themselves: HdrMeta i, and the 320 code lengths as nibbles in HDR_LW words at
-// lens[i * HDR_LW] (slot s in bits [4 (s & 7), +4) of word s >> 3).  The scratch buffer holds the
-// tail descriptors, the metas and the length words, in that order (INFLATE_SCRATCH_BYTES).
+// lens[i * HDR_LW] (slot s in bits [4 (s & 7), +4) of word s >> 3).  The meta also carries the
+// number of codes of each length (round 10): the lane adds them up while it decodes the lengths,
+// so the tail kernel's table build starts from the counts instead of counting the 320 lengths again.
+// The scratch buffer holds the tail descriptors, the metas and the length words, in that order
+// (INFLATE_SCRATCH_BYTES).
 // DQ_HDR_PREPASS = 0: no pre-pass, every header is decoded where it is used (round 8).
 #ifndef DQ_HDR_PREPASS
 #define DQ_HDR_PREPASS 1
@@ -188,7 +191,13 @@ struct alignas(16) HdrMeta {
   uint32_t info;    // kind (bits 0-1), bfinal (2), ndist (3-7), nlen (8-16), status (24-31)
   uint32_t end;     // HDR_DYN: bit position after the header
   uint32_t pad[2];
+  // HDR_DYN: the codes of length l (1..15) in the 16-bit field l (bits [16 (l & 1), +16) of word
+  // l >> 1): litlen codes (<= 286) in its bits 0-8, distance codes (<= 30) in bits 9-13; field 0
+  // is zero
+  uint32_t cnt[8];
 };
+DQ_HD int hm_cnt_ll(uint32_t field) { return (int)(field & 511u); }
+DQ_HD int hm_cnt_d(uint32_t field) { return (int)((field >> 9) & 31u); }
 static_assert(sizeof(TailDesc) + sizeof(HdrMeta) + 4 * HDR_LW == INFLATE_SCRATCH_BYTES, "scratch per block");
 DQ_HD int hm_kind(uint32_t info) { return (int)(info & 3u); }
 DQ_HD int32_t hm_bfinal(uint32_t info) { return (int32_t)((info >> 2) & 1u); }
@@ -886,6 +895,10 @@ DQ_AI uint16_t clt_entry(const uint8_t* clen, int t, bool* okp) {
 
 // Build both decode tables from L.u.d.x.h.lens (all threads; barriers inside).
 // Litlen symbols are handled by threads 0..319 (waves 0-4), distance symbols by wave 5.
+// (The ranks need the per-wave counts whatever the header's source, so a pre-decoded header's
+// counts of each code length, HdrMeta.cnt, would save only the five-word sum and one barrier of
+// canon_from_counts: measured, the block kernel was slower with that path than without, DESIGN.md
+// "Round 10".  Only the tail kernel takes them.)
 DQ_AI void build_tables(LdsI& L, int nlen, int ndist) {
   const int t = tid_fresh(), lane = t & 63, wv = t >> 6;
   // second-level tables (the roots are written whole); their first entries are invalid-code
@@ -2099,89 +2112,176 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
 // One lane per launched BGZF block, one wave per workgroup.  Lane i decodes the header of block
 // sel[i] (or i) at the start of its deflate data -- or, TAIL, at tails[i].pos where tails[i].flag
 // is set -- with dq_hdr_core.h's serial decoder, and writes record i (HdrMeta, HDR_LW length
-// words).  Per lane in LDS: the 128 one-byte entries of the code-length code's decode table
-// (entry k at k * 64 + lane) and the HDR_LW length words (word w at w * HP_LS + lane; HP_LS odd, so
-// the write-out's reads, 64 consecutive global words = 1.6 records per instruction, spread over
-// the banks).  The lengths leave the wave as HDR_LW stores of 64 consecutive words: a lane's own
-// 160 bytes written from its registers would be 64 scattered lines per store.
+// words).  The 64 lanes run 64 different headers in lock step: the wave executes every branch some
+// lane takes, in every turn of the length loop, so what a turn costs is the sum of its paths and
+// the kernel is shaped to keep that sum, and the waits in it, small (round 10):
+//   - the compressed words come from a window of HP_WIN words per lane in registers (HpSrc), moved
+//     by all lanes at once a few times per header.  (Round 9 loaded one word per 32 bits behind the
+//     bit reader's branch: out of phase over the lanes, nearly every turn waited for some lane's
+//     load);
+//   - a run of equal lengths goes to the sink as one pattern of nibbles, not slot by slot;
+//   - per lane in LDS only the 128 one-byte entries of the code-length code's decode table (entry k
+//     at k * 64 + lane), 8 KB per wave: HP_WAVES waves fit a CU (round 9 also staged the length words
+//     there, 18.6 KB and 8 waves);
+//   - the length words leave the lane as it fills them, two to an 8-byte store into its own record
+//     (HpSink; 64 records = 64 lines per store instruction, twenty stores per header);
+//   - the numbers of codes of each length are summed in registers and stored in the meta.
 // The reads: 32-bit words between the word of the header's first bit and HDR_WORDS - 1 words after
 // it, the range the block and tail kernels stage (C's pad covers it at the end of the file).
-constexpr int HP_LS = 65;
+constexpr int HP_WIN = 16;    // words per lane in the window
+constexpr int HP_WAVES = 16;  // waves (one-wave workgroups) per CU
 struct HpSrc {
   const uint32_t* __restrict__ W;
   uint32_t last;  // the last word the header may read
-  DQ_AI uint32_t word(uint32_t i) const {
-    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(W) + (min(i, last) << 2));
+  uint32_t base;  // word index of w[0]
+  uint32_t w[HP_WIN];
+  DQ_AI void load(uint32_t b0) {  // one round trip
+    base = b0;
+#pragma unroll
+    for (int k = 0; k < HP_WIN; k++)
+      w[k] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(W) + (min(b0 + (uint32_t)k, last) << 2));
+  }
+  // hdr_decode asks for at most one word before the next call: word i + 1 is inside the window
+  DQ_AI void ahead(uint32_t i) {
+    if (__any(i - base >= (uint32_t)(HP_WIN - 1))) load(i);
+  }
+  DQ_AI uint32_t word(uint32_t i) const {  // base <= i < base + HP_WIN
+    const uint32_t k = i - base;
+    DQ_CHK(k < (uint32_t)HP_WIN, CHK_K2_BITS);
+    uint32_t t[HP_WIN];
+#pragma unroll
+    for (int j = 0; j < HP_WIN; j++) t[j] = w[j];
+#pragma unroll
+    for (int h = HP_WIN / 2, bit = 1; h >= 1; h /= 2, bit *= 2)
+#pragma unroll
+      for (int j = 0; j < h; j++) t[j] = (k & (uint32_t)bit) ? t[2 * j + 1] : t[2 * j];
+    return t[0];
   }
 };
+static_assert(HP_WIN >= 8 && (HP_WIN & (HP_WIN - 1)) == 0, "six words before the first ahead(); a tree of selects");
 struct HpTbl {
   uint8_t* t;  // + lane
   DQ_AI void set(uint32_t k, uint32_t v) { t[k * 64] = (uint8_t)v; }
   DQ_AI uint32_t get(uint32_t k) const { return t[k * 64]; }
 };
-struct HpSink {  // slots come in increasing order: a word is stored when the next one begins
-  uint32_t* w;   // + lane
-  uint32_t cur, acc;
-  DQ_AI void put(uint32_t i, uint32_t v) {
-    if ((i >> 3) != cur) {
-      flush();
-      cur = i >> 3;
+// Runs come with increasing slots: a unit of two length words (16 slots) is stored when a run
+// begins in a later one, and the units between them, which hold no length, as zeros (the record
+// holds an earlier header's).
+template <bool TIMING>
+struct HpSink {
+  uint2* out;      // this record's HDR_LW / 2 units
+  uint32_t cur;    // the unit being filled: those before it are stored
+  uint64_t acc;
+  uint64_t c[4];   // HdrMeta.cnt: the field of length l in bits [16 (l & 3), +16) of c[l >> 2]
+  uint64_t tm[3];  // TIMING: s_memtime at hdr_decode's marks
+  DQ_AI void store() {
+    DQ_CHK(cur < (uint32_t)(HDR_LW / 2), CHK_K2_LANES);
+    out[cur] = make_uint2((uint32_t)acc, (uint32_t)(acc >> 32));
+  }
+  DQ_AI void run(uint32_t i, uint32_t n, uint32_t v) {  // i + n <= HDR_LENS, n <= 6
+    const uint32_t u = i >> 4, p = i & 15;
+    if (u != cur) {  // u > cur
+      store();
+      for (uint32_t k = cur + 1; k < u; k++) out[k] = make_uint2(0, 0);
+      cur = u;
       acc = 0;
     }
-    acc |= v << (4 * (i & 7));
+    const uint64_t pat = (v * 0x111111u) & ((1u << (4 * n)) - 1);
+    acc |= pat << (4 * p);
+    if (p + n > 16) {  // the run goes on in the next unit (p >= 11; u + 1 < HDR_LW / 2 as i + n <= HDR_LENS)
+      store();
+      cur = u + 1;
+      acc = pat >> (4 * (16 - p));
+    }
+    const uint64_t x = (uint64_t)(i < 288 ? n : n << 9) << (16 * (v & 3));
+#pragma unroll
+    for (int k = 0; k < 4; k++) c[k] += (v >> 2) == (uint32_t)k ? x : 0ull;
   }
-  DQ_AI void flush() {
-    if (acc) w[cur * HP_LS] = acc;
+  DQ_AI void mark(int k) {
+    if (TIMING) tm[k] = __builtin_amdgcn_s_memtime();
+  }
+  DQ_AI void finish() {
+    store();
+    for (uint32_t k = cur + 1; k < (uint32_t)(HDR_LW / 2); k++) out[k] = make_uint2(0, 0);
   }
 };
+static_assert(HDR_LW % 2 == 0 && dqh::HDR_LENS == 16 * (HDR_LW / 2), "whole units of two length words");
+DQ_AI uint64_t wave_max_u64(uint64_t v) {
+  for (int d = 32; d; d >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(v >> 32), d, 64);
+    v = max(v, (uint64_t)hi << 32 | lo);
+  }
+  return v;
+}
 
-template <bool TAIL>
-__global__ __launch_bounds__(64) void inflate_header_kernel(
+// tim (TIMING): eight words per wave at tim[8 (2 wave + TAIL)], by lane 0: the cycles of the address
+// loads, of the code-length code's lengths (with the round trip of the first words), of its table,
+// of the length loop and of the write-out; [5] = 1
+template <bool TAIL, bool TIMING>
+__global__ __launch_bounds__(64, HP_WAVES / 4) void inflate_header_kernel(
     const uint8_t* __restrict__ C, const int64_t* __restrict__ blk_pos,
     const int32_t* __restrict__ blk_csize, int64_t ngrid, const int32_t* __restrict__ sel,
-    const TailDesc* __restrict__ tails, HdrMeta* __restrict__ hdr) {
+    const TailDesc* __restrict__ tails, HdrMeta* __restrict__ hdr, uint64_t* __restrict__ tim) {
   __shared__ uint8_t clt[128 * 64];
-  __shared__ uint32_t lw[HDR_LW * HP_LS];
+  static_assert(HP_WAVES * sizeof(clt) <= 160 * 1024 && HP_WAVES <= 32, "HP_WAVES one-wave workgroups per CU");
+  const uint64_t t0 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
   const int lane = (int)threadIdx.x;
   const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + lane;
   bool act = i < ngrid;
-  uint32_t pos = 0;
-  if (TAIL && act) {
-    const TailDesc td = tails[i];
-    act = td.flag == 1;
-    pos = (uint32_t)td.pos;
-  }
-  for (int w = 0; w < HDR_LW; w++) lw[w * HP_LS + lane] = 0;
-  dqh::HdrInfo R = {dqh::HDR_NONE, 0, 0, 0, 0, 0};
+  // the tail descriptor and the block's place, in one round trip (after the selection's)
+  TailDesc td = {0, 0, 0, 0};
+  int64_t bpos = 0;
+  int32_t csize = 0;
   if (act) {
+    if (TAIL) td = tails[i];
     const int64_t b = sel ? (int64_t)sel[i] : i;
-    const uint8_t* dp = C + blk_pos[b] + 18;  // as the block kernel: bit positions from the
+    bpos = blk_pos[b];
+    csize = blk_csize[b];
+  }
+  if (TAIL) act = act && td.flag == 1;
+  uint64_t t1 = 0;
+  HpSink<TIMING> K;
+  K.tm[0] = K.tm[1] = K.tm[2] = 0;
+  if (act) {
+    const uint8_t* dp = C + bpos + 18;  // as the block kernel: bit positions from the
     const int mis = (int)(reinterpret_cast<uintptr_t>(dp) & 15);  // 16-byte aligned base
     const uint32_t a0 = 8u * (uint32_t)mis;
-    const uint32_t endbits = a0 + 8u * (uint32_t)max(blk_csize[b] - 26, 0);
-    if (!TAIL) pos = a0;
-    const HpSrc S{reinterpret_cast<const uint32_t*>(dp - mis), (pos >> 5) + dqh::HDR_WORDS - 1};
+    const uint32_t endbits = a0 + 8u * (uint32_t)max(csize - 26, 0);
+    const uint32_t pos = TAIL ? (uint32_t)td.pos : a0;
+    HpSrc S;
+    S.W = reinterpret_cast<const uint32_t*>(dp - mis);
+    S.last = (pos >> 5) + dqh::HDR_WORDS - 1;
+    S.load(pos >> 5);
+    if (TIMING) t1 = __builtin_amdgcn_s_memtime();
     HpTbl T{clt + lane};
-    HpSink K{lw + lane, 0, 0};
-    R = dqh::hdr_decode(S, T, K, pos, endbits);
-    K.flush();
-    HdrMeta m;
-    m.info = (uint32_t)R.kind | (uint32_t)R.bfinal << 2 | (uint32_t)(R.ndist & 31) << 3 |
-             (uint32_t)(R.nlen & 511) << 8 | (uint32_t)R.status << 24;
-    m.end = R.end;
-    m.pad[0] = m.pad[1] = 0;
-    hdr[i] = m;
+    HdrMeta* const rec = hdr + i;
+    K.out = reinterpret_cast<uint2*>(reinterpret_cast<uint32_t*>(hdr + ngrid) + i * HDR_LW);
+    K.cur = 0;
+    K.acc = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) K.c[k] = 0;
+    const dqh::HdrInfo R = dqh::hdr_decode(S, T, K, pos, endbits);
+    if (R.kind == dqh::HDR_DYN) K.finish();
+    const uint32_t info = (uint32_t)R.kind | (uint32_t)R.bfinal << 2 | (uint32_t)(R.ndist & 31) << 3 |
+                          (uint32_t)(R.nlen & 511) << 8 | (uint32_t)R.status << 24;
+    uint4* const m = reinterpret_cast<uint4*>(rec);
+    m[0] = make_uint4(info, R.end, 0, 0);
+    m[1] = make_uint4((uint32_t)K.c[0], (uint32_t)(K.c[0] >> 32), (uint32_t)K.c[1], (uint32_t)(K.c[1] >> 32));
+    m[2] = make_uint4((uint32_t)K.c[2], (uint32_t)(K.c[2] >> 32), (uint32_t)K.c[3], (uint32_t)(K.c[3] >> 32));
   }
-  // the length words of this wave's records: HDR_LW * 64 consecutive global words (records that
-  // hold no decoded header are not written)
-  __syncthreads();
-  const uint64_t dyn = __ballot(R.kind == dqh::HDR_DYN);
-  uint32_t* out = reinterpret_cast<uint32_t*>(hdr + ngrid) + i0 * HDR_LW;
-  for (int k = 0; k < HDR_LW; k++) {
-    const int g = 64 * k + lane, r = g / HDR_LW, w = g - r * HDR_LW;
-    if ((dyn >> r) & 1) out[g] = lw[w * HP_LS + r];
+  if (TIMING) {
+    const uint64_t tend = __builtin_amdgcn_s_memtime();
+    uint64_t tp[5] = {t0, wave_max_u64(t1), wave_max_u64(K.tm[0]), wave_max_u64(K.tm[1]), wave_max_u64(K.tm[2])};
+    for (int k = 1; k < 5; k++) tp[k] = max(tp[k], tp[k - 1]);  // a mark no lane reached: an empty phase
+    if (lane == 0) {
+      uint64_t* o = tim + 8 * (2 * (int64_t)blockIdx.x + (TAIL ? 1 : 0));
+      for (int k = 0; k < 4; k++) o[k] = tp[k + 1] - tp[k];
+      o[4] = tend - tp[4];
+      o[5] = 1;
+    }
   }
 }
+static_assert(sizeof(HdrMeta) == 48 && offsetof(HdrMeta, cnt) == 16, "the pre-pass stores the meta as three uint4");
 
 // ================================================================ the tail kernel
 // Per-wave LDS of inflate_tail_kernel (~13 KB: four tails per workgroup, three workgroups per CU).
@@ -2312,19 +2412,21 @@ DQ_AI uint32_t read_lengths_wave(LdsW& L, uint32_t P, int nlen, int ndist, uint3
 // The decode tables by one wave: root tables as the block kernel's (entries carry the decoded
 // values), and the canonical slow path (E_SLOW) for every root prefix of a longer code -- a tail
 // decodes ~700 symbols, so the second-level tables are not worth their build.  Sets M_SLOW.
-DQ_AI void build_tables_wave(LdsW& L, int nlen, int ndist) {
+// counted: H.cnt already holds the numbers of codes of each length (a header of the pre-pass, whose
+// record carries them: each lane below 32 wrote its own entry).
+DQ_AI void build_tables_wave(LdsW& L, int nlen, int ndist, bool counted) {
   const int lane = tid_fresh() & 63;
   auto& H = L.u.d.x.h;
-  if (lane < 32) {
-    H.cnt[lane] = 0;
-    H.run[lane] = 0;
-  }
-  __builtin_amdgcn_wave_barrier();
-  // code-length counts of both alphabets (LDS atomics: one pass over the symbols)
-  for (int k = lane; k < 320; k += 64) {
-    const bool isl = k < 288;
-    const int len = isl ? (k < nlen ? H.lens[k] : 0) : (k - 288 < ndist ? H.lens[k] : 0);
-    if (len) atomicAdd(&H.cnt[(isl ? 0 : 16) + len], 1);
+  if (lane < 32) H.run[lane] = 0;
+  if (!counted) {
+    if (lane < 32) H.cnt[lane] = 0;
+    __builtin_amdgcn_wave_barrier();
+    // code-length counts of both alphabets (LDS atomics: one pass over the symbols)
+    for (int k = lane; k < 320; k += 64) {
+      const bool isl = k < 288;
+      const int len = isl ? (k < nlen ? H.lens[k] : 0) : (k - 288 < ndist ? H.lens[k] : 0);
+      if (len) atomicAdd(&H.cnt[(isl ? 0 : 16) + len], 1);
+    }
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -2502,14 +2604,19 @@ __global__ __launch_bounds__(64 * TW, 4) void inflate_tail_kernel(
   uint32_t hinfo = 0, hend = 0;
   if (sflags & 32) {  // the records follow the tail descriptors
     const HdrMeta* hdr = reinterpret_cast<const HdrMeta*>(tails + ngrid);
-    const HdrMeta hm = hdr[gi];
-    hinfo = hm.info;
-    hend = hm.end;
+    hinfo = hdr[gi].info;
+    hend = hdr[gi].end;
     if (hm_kind(hinfo) == dqh::HDR_DYN && lane < HDR_LW) {
       const uint32_t w = reinterpret_cast<const uint32_t*>(hdr + ngrid)[gi * HDR_LW + lane];
       uint32_t* l8 = reinterpret_cast<uint32_t*>(L.u.d.x.h.lens);
       l8[2 * lane] = nib4(w & 0xffffu);
       l8[2 * lane + 1] = nib4(w >> 16);
+      // the numbers of codes of each length, where build_tables_wave counts them (lane l: litlen
+      // length l, lane 16 + l: distance length l); they stay there as the lengths do
+      if (lane < 32) {
+        const uint32_t f = reinterpret_cast<const uint16_t*>(hdr[gi].cnt)[lane & 15];
+        L.u.d.x.h.cnt[lane] = lane < 16 ? hm_cnt_ll(f) : hm_cnt_d(f);
+      }
     }
     if (hm_kind(hinfo) == dqh::HDR_ERR && lane == 0) L.misc[M_ERR] = hm_status(hinfo);
   }
@@ -2620,7 +2727,7 @@ __global__ __launch_bounds__(64 * TW, 4) void inflate_tail_kernel(
     }
     tick(0);
     // ---- tables
-    build_tables_wave(L, nlen, ndist);
+    build_tables_wave(L, nlen, ndist, hpre && pos == (uint32_t)td.pos);
     if (L.misc[M_ERR]) break;
     __builtin_amdgcn_wave_barrier();
     const bool slow = L.misc[M_SLOW] != 0;
@@ -3056,9 +3163,15 @@ void launch_inflate3(const uint8_t* C, const int64_t* blk_pos, const int32_t* bl
   if (td) (void)hipMemsetAsync(td, 0, sizeof(TailDesc) * (size_t)ngrid, s);
   const dim3 hgrid((unsigned)((ngrid + 63) / 64));
   // the headers of the first deflate blocks, one lane per block
-  if (hm)
-    hipLaunchKernelGGL((inflate_header_kernel<false>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid, sel,
-                       (const TailDesc*)nullptr, hm);
+  // (DQ_TIMING: the pre-pass's phases follow the block and tail kernels', 16 words per wave)
+  uint64_t* const htim = tim ? tim + (TIM_W + 16) * ngrid : nullptr;
+  static_assert(TIM_W + 16 + 16 <= INFLATE_TIM_WORDS, "timing words per block");
+  if (hm && tim)
+    hipLaunchKernelGGL((inflate_header_kernel<false, true>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid,
+                       sel, (const TailDesc*)nullptr, hm, htim);
+  else if (hm)
+    hipLaunchKernelGGL((inflate_header_kernel<false, false>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid,
+                       sel, (const TailDesc*)nullptr, hm, htim);
 #define DQ_LAUNCH(TM, NBT, GT)                                                                  \
   hipLaunchKernelGGL((inflate_block_kernel<TM, NBT, GT>), dim3((unsigned)ngrid), dim3(WG), ldspad, s, C, \
                      blk_pos, blk_csize, blk_usize, uoff, ngrid, U, status, verify_crc, crc_init, tim, ov, \
@@ -3070,11 +3183,14 @@ void launch_inflate3(const uint8_t* C, const int64_t* blk_pos, const int32_t* bl
     DQ_LAUNCH(false, DQ_RES_NB, DQ_RES_G);
 #undef DQ_LAUNCH
   // the headers of the deferred tails, into the records the block kernel has consumed
-  if (td && hm)
-    hipLaunchKernelGGL((inflate_header_kernel<true>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid, sel,
-                       (const TailDesc*)td, hm);
+  if (td && hm && tim)
+    hipLaunchKernelGGL((inflate_header_kernel<true, true>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid,
+                       sel, (const TailDesc*)td, hm, htim);
+  else if (td && hm)
+    hipLaunchKernelGGL((inflate_header_kernel<true, false>), hgrid, dim3(64), 0, s, C, blk_pos, blk_csize, ngrid,
+                       sel, (const TailDesc*)td, hm, htim);
   // DQ_TIMING: the block kernel's phases in tim[0, TIM_W ngrid), the tail kernel's in the 16 ngrid
-  // words after them (16 per tail; dq_api allocates TIM_W + 16 per block)
+  // words after them (16 per tail; dq_api allocates INFLATE_TIM_WORDS per block)
   if (td && tim)
     hipLaunchKernelGGL((inflate_tail_kernel<true>), dim3((unsigned)((ngrid + TW - 1) / TW)), dim3(64 * TW), 0, s,
                        C, blk_pos, blk_csize, blk_usize, uoff, ngrid, U, status, verify_crc, crc_init,

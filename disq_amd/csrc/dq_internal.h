@@ -29,10 +29,12 @@ enum : int32_t {
 // DQ_CHK compiles to nothing.
 enum : int {
   CHK_K1_SLOT = 0,   // K1: a candidate's slot outside its chunk's CAP slots
-  CHK_K2_BITS = 1,   // K2: the bit reader loads a word past the member's deflate data (+ slack)
+  CHK_K2_BITS = 1,   // K2: the bit reader loads a word past the member's deflate data (+ slack);
+                     // the header pre-pass asks for a word outside its lane's window
   CHK_K2_IMAGE = 2,  // K2: an emit / stored-copy store outside the LDS output image
   CHK_K2_TABLE = 3,  // K2: a second-level table read outside its alphabet's area
-  CHK_K2_LANES = 4,  // K2: per-lane arrays / redo list outside the image tail
+  CHK_K2_LANES = 4,  // K2: per-lane arrays / redo list outside the image tail; the header pre-pass
+                     //     stores length words outside its lane's record
   CHK_K2_BM = 5,     // K2: a match-start bitmap word outside the bitmap, or a resolve group of four
                      //     bytes whose start bits are not 0, 1, 2, 4, 8 or 9 (matches are >= 3 long)
   CHK_K2_NXT = 6,    // K2: a resolve next pointer outside the batch window
@@ -154,9 +156,12 @@ void launch_exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, int64
 // safe) and returns that device's table of x^(8n) * ~0 mod P, n = 0..65536 (nullptr on failure).
 const uint32_t* inflate3_tables(int device);
 // scratch: INFLATE_SCRATCH_BYTES of device memory per launched block (16-byte aligned): the tail
-// kernel's descriptors (16 bytes each), then the header pre-pass's records (16 bytes and the 320
-// code lengths as nibbles each); nullptr: the block kernel decodes every deflate block itself
-constexpr size_t INFLATE_SCRATCH_BYTES = 16 + 16 + 160;
+// kernel's descriptors (16 bytes each), then the header pre-pass's records (16 bytes, 32 bytes of
+// code-length counts and the 320 code lengths as nibbles each); nullptr: the block kernel decodes
+// every deflate block itself.
+// tim (DQ_TIMING, else nullptr): INFLATE_TIM_WORDS 64-bit words per launched block, zero filled
+constexpr size_t INFLATE_SCRATCH_BYTES = 16 + (16 + 32) + 160;
+constexpr size_t INFLATE_TIM_WORDS = 64;  // 32 per block, 16 per tail, 16 per 64 blocks of the pre-pass
 void launch_inflate3(const uint8_t* C, const int64_t* blk_pos, const int32_t* blk_csize,
                      const int32_t* blk_usize, const int64_t* uoff, int64_t nblk, uint8_t* U,
                      int32_t* status, int32_t verify_crc, const uint32_t* crc_init, uint64_t* tim,
