@@ -7,6 +7,8 @@ BSIZE = member length - 1, CRC32 and ISIZE trailer) and ends with the 28-byte EO
 import struct
 import zlib
 
+import reccases
+
 EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 BLOCK_U = 65280  # htsjdk BlockCompressedStreamConstants.DEFAULT_UNCOMPRESSED_BLOCK_SIZE
 
@@ -69,9 +71,6 @@ def qual_offset(rec: bytes) -> int:
 def make_record(ref_id, pos, name: bytes, l_seq, flag=0, mapq=60, base=0x11, qual=30,
                 next_ref_id=-1, next_pos=-1, tlen=0) -> bytes:
     """A mapped record with one M cigar op over l_seq bases (all one base, constant quality)."""
-    rn = name + b"\x00"
-    cigar = struct.pack("<I", (l_seq << 4) | 0)
-    seq = bytes([base]) * ((l_seq + 1) // 2)
-    body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(rn), mapq, 4680, 1, flag, l_seq,
-                       next_ref_id, next_pos, tlen) + rn + cigar + seq + bytes([qual]) * l_seq
-    return struct.pack("<i", len(body)) + body
+    return reccases.record(ref_id, pos, name + b"\x00", [(l_seq, 0)], l_seq, flag=flag, mapq=mapq,
+                           bin=4680, next_ref=next_ref_id, next_pos=next_pos, tlen=tlen,
+                           seq=bytes([base]) * ((l_seq + 1) // 2), qual=bytes([qual]) * l_seq)

@@ -26,7 +26,10 @@ def gpu_read(data, split=0, nio=False, traversal=None, bai=None, verify_crc=True
         return c.read(with_raw=True, traversal=traversal), c.plan(), c.inflated()
 
 
-def assert_parity(data, split=0, nio=False, traversal=None, bai=None):
+def assert_parity(data, split=0, nio=False, traversal=None, bai=None, raw_check=50):
+    """raw_check: how many records (evenly spaced) have their raw bytes hashed again by the oracle;
+    None: every record.  (A traversal here goes through dq_read: the whole-file pipeline and the
+    interval filter over its records, never the .bai span run of dq_run_resident.)"""
     ob = O.OracleBam(data)
     parts = ob.read_partitions(split, nio=nio, traversal=traversal, bai=bai)
     b, plan, u = gpu_read(data, split, nio, traversal, bai)
@@ -43,7 +46,8 @@ def assert_parity(data, split=0, nio=False, traversal=None, bai=None):
             assert np.array_equal(b[f][lo:hi], p[f]), (i, f)
         assert int(b["part_digest"][i]) == O.stream_digest(p["hash"])
     # raw bytes reproduce the hashes
-    for k in np.linspace(0, len(b["voffset"]) - 1, num=min(50, len(b["voffset"])), dtype=int):
+    nrec = len(b["voffset"])
+    for k in np.linspace(0, nrec - 1, num=nrec if raw_check is None else min(raw_check, nrec), dtype=int):
         o = int(b["raw_offset"][k])
         n = 4 + int(b["block_size"][k])
         assert O.record_hash(bytes(b["raw"][o:o + n])) == int(b["hash"][k])
