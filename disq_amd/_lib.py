@@ -127,6 +127,24 @@ class DqInfoBatch(C.Structure):
                 ("n_float_host", C.c_int64)]
 
 
+class DqTagKey(C.Structure):
+    _fields_ = [("id", C.c_char_p), ("type", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DqTagBatch(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("n_keys", C.c_int32), ("reserved", C.c_int32),
+                ("key_type", C.POINTER(C.c_int32)), ("key_base", C.POINTER(C.c_int64)),
+                ("flags", C.POINTER(C.c_uint8)), ("vtype", C.POINTER(C.c_uint8)),
+                ("subtype", C.POINTER(C.c_uint8)), ("val_off", C.POINTER(C.c_int32)),
+                ("val_len", C.POINTER(C.c_int32)),
+                ("val", C.POINTER(C.c_uint32)), ("n_val", C.c_int64),
+                ("n_partitions", C.c_int64), ("part_offset", C.POINTER(C.c_int64))]
+
+
+# dq_tag_key.type and dq_tag_batch.flags (include/disq_gpu.h)
+TAG_ANY, TAG_INT, TAG_FLOAT, TAG_CHAR, TAG_STRING = 0, 1, 2, 3, 4
+TAG_PRESENT, TAG_REPEATED = 1, 4
+
 # dq_info_key.type, dq_info_batch.flags and the missing values (include/disq_gpu.h)
 INFO_AUTO, INFO_FLAG, INFO_INTEGER, INFO_FLOAT, INFO_STRING = 0, 1, 2, 3, 4
 INFO_PRESENT, INFO_HAS_VALUE, INFO_REPEATED = 1, 2, 4
@@ -187,7 +205,7 @@ EXPORTS = ("dq_ctx_create", "dq_ctx_destroy", "dq_last_error", "dq_version", "dq
            "dq_sam_read", "dq_sam_write", "dq_sam_write_resident", "dq_sam_write_fetch",
            "dq_vcf_run", "dq_vcf_read", "dq_variant_batch_free", "dq_vcf_genotypes_run",
            "dq_vcf_genotypes", "dq_genotype_batch_free", "dq_vcf_info_run", "dq_vcf_info",
-           "dq_info_batch_free")
+           "dq_info_batch_free", "dq_tags_run", "dq_tags", "dq_tag_batch_free")
 
 _lib = None
 _lock = threading.Lock()
@@ -267,6 +285,9 @@ def lib():
         L.dq_vcf_info_run.argtypes = [vp, P(DqInfoKey), C.c_int32, P(DqStats)]
         L.dq_vcf_info.argtypes = [vp, P(DqInfoKey), C.c_int32, P(P(DqInfoBatch))]
         L.dq_info_batch_free.argtypes = [P(DqInfoBatch)]
+        L.dq_tags_run.argtypes = [vp, P(DqTraversal), P(DqTagKey), C.c_int32, P(DqStats)]
+        L.dq_tags.argtypes = [vp, P(DqTraversal), P(DqTagKey), C.c_int32, P(P(DqTagBatch))]
+        L.dq_tag_batch_free.argtypes = [P(DqTagBatch)]
         L.dq_sam_open_memory.argtypes = [vp, vp, C.c_int64]
         L.dq_sam_open_path.argtypes = [vp, C.c_char_p]
         L.dq_sam_run.argtypes = [vp, P(DqStats)]
@@ -924,6 +945,81 @@ class Context:
         check(self._h, lib().dq_read(self._h, C.byref(t) if t is not None else None,
                                      export_mode(with_raw), C.byref(bp)))
         return batch_to_numpy(bp, self)
+
+    # ---- BAM aux tag decode (dq_tags*) of an open BAM or SAM context
+    @staticmethod
+    def _tag_keys(keys):
+        """keys: ids (str or bytes) or (id, TAG_* class) pairs, as a dq_tag_key array and the ids."""
+        ids, arr = [], (DqTagKey * max(1, len(keys)))()
+        for q, k in enumerate(keys):
+            vid, ty = (k, TAG_ANY) if isinstance(k, (str, bytes)) else k
+            vid = vid.encode() if isinstance(vid, str) else bytes(vid)
+            if b"\0" in vid:
+                raise ValueError("a tag id holds a NUL byte")
+            ids.append(vid)
+            arr[q] = DqTagKey(vid, int(ty), 0)
+        return arr, ids
+
+    def tags_run(self, keys, traversal=None):
+        """The pipeline as read() (sam_read()) runs it, then the tag check and decode passes for
+        these keys; the columns stay in HBM (dq_tags_run).  ms_records is the device time of the
+        records stage plus the two tag passes."""
+        arr, ids = self._tag_keys(keys)
+        t, keep = self._traversal(traversal)
+        st = DqStats()
+        check(self._h, lib().dq_tags_run(self._h, C.byref(t) if t is not None else None, arr, len(ids),
+                                         C.byref(st)))
+        return st
+
+    def tags(self, keys, traversal=None):
+        """The aux tags of read(traversal=...)'s records (sam_read()'s on a SAM context, where
+        traversal must be None) for these keys (dq_tags): dict of numpy arrays -- flags, vtype,
+        subtype, val_off and val_len shaped (K, n), key_type and key_base shaped (K,), val flat
+        (uint32), part_offset -- plus keys (the ids, bytes) and values: per key a copy of its block
+        of val shaped (n,), float32 for a TAG_FLOAT key, uint8 for a TAG_CHAR key, and for a
+        TAG_INT key int32 -- or uint32 when a present cell of the key is stored as 'I' with its top
+        bit set, so that no value changes sign (vtype[q] tells per row how a value was stored) --
+        and None for a TAG_ANY or TAG_STRING key, whose access path is the span val_off / val_len
+        into the record's raw bytes."""
+        arr, ids = self._tag_keys(keys)
+        t, keep = self._traversal(traversal)
+        bp = C.POINTER(DqTagBatch)()
+        check(self._h, lib().dq_tags(self._h, C.byref(t) if t is not None else None, arr, len(ids),
+                                     C.byref(bp)))
+        try:
+            b = bp.contents
+            n, K = b.n_records, b.n_keys
+
+            def arr_of(ptr, k, dt):
+                if not k or not ptr:
+                    return np.zeros(0, dt)
+                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
+            g = {"flags": arr_of(b.flags, K * n, np.uint8).reshape(K, n),
+                 "vtype": arr_of(b.vtype, K * n, np.uint8).reshape(K, n),
+                 "subtype": arr_of(b.subtype, K * n, np.uint8).reshape(K, n),
+                 "val_off": arr_of(b.val_off, K * n, np.int32).reshape(K, n),
+                 "val_len": arr_of(b.val_len, K * n, np.int32).reshape(K, n),
+                 "key_type": arr_of(b.key_type, K, np.int32), "key_base": arr_of(b.key_base, K, np.int64),
+                 "val": arr_of(b.val, b.n_val, np.uint32),
+                 "part_offset": arr_of(b.part_offset, b.n_partitions + 1, np.int64), "keys": ids}
+            vals = []
+            for q in range(K):
+                ty, at = int(g["key_type"][q]), int(g["key_base"][q])
+                if at < 0:
+                    vals.append(None)
+                    continue
+                v = g["val"][at:at + n]
+                if ty == TAG_FLOAT:
+                    vals.append(v.view(np.float32).copy())
+                elif ty == TAG_CHAR:
+                    vals.append(v.astype(np.uint8))
+                else:
+                    big = bool(np.any((g["vtype"][q] == ord("I")) & (v >= 1 << 31)))
+                    vals.append(v.copy() if big else v.view(np.int32).copy())
+            g["values"] = vals
+            return g
+        finally:
+            lib().dq_tag_batch_free(bp)
 
     def run_resident(self, traversal=None):
         st = DqStats()

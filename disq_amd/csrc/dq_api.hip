@@ -28,6 +28,7 @@
 #include "../../include/disq_gpu.h"
 #include "dq_internal.h"
 #include "dq_sam_core.h"
+#include "dq_tags_core.h"
 #include "dq_vcf_core.h"
 #include "dq_vcf_gt_core.h"
 #include "dq_vcf_info_core.h"
@@ -123,8 +124,8 @@ struct Bai {
 struct dq_ctx {
   dq_opts o{};
   hipStream_t s = nullptr;
-  hipEvent_t ev[20] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes;
-                           // 16..19: the INFO passes
+  hipEvent_t ev[24] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes;
+                           // 16..19: the INFO passes; 20..23: the tag passes
   // DQ_EXPORT_STREAMS=2: the export's device-to-pinned copies alternate between s and this second
   // stream (a second DMA engine); created on first use
   hipStream_t sx = nullptr;
@@ -195,6 +196,13 @@ struct dq_ctx {
   unsigned long long sam_init[4] = {~0ull, 0, 0, 0};  // first failing line | undecided | fix-ups
   DevBuf s_ls, s_vs, s_vl, s_splits, s_status, s_size, s_fix, s_refs, sam_rec;
   dqt::NameTable sam_refs{};
+  // BAM aux tag decode (dq_tags*) behind the records stage: the row list, the key table, the columns
+  // of the last call (tag_n rows, tag_type.size() keys) and its partitions' bounds
+  DevBuf a_idx, a_keys, a_scal, a_base, a_flags, a_vtype, a_sub, a_off, a_len, a_val;
+  int64_t tag_n = 0, tag_nval = 0;
+  std::vector<int32_t> tag_type;
+  std::vector<int64_t> tag_base, tag_bounds;
+  double tag_ms = 0;
   // SAM writer (dq_sam_write*): the uploaded records and offsets, per record status / line size /
   // line offset, the reference names, the text (w_len bytes)
   DevBuf w_in, w_off, w_status, w_size, w_loff, w_refs, w_scal, w_out;
@@ -2693,6 +2701,35 @@ static int check_tail_reachable(dq_ctx* ctx, const dq_traversal* tr) {
   return 0;
 }
 
+// The rows of dq_read(ctx, tr): the pipeline run, then every partition's record range (tr == NULL:
+// ranges) or its filtered record indices (idx), and the partitions' bounds in the row list.
+static int read_rows(dq_ctx* ctx, const dq_traversal* tr, std::vector<std::pair<int64_t, int64_t>>& ranges,
+                     std::vector<int64_t>& idx, std::vector<int64_t>& bounds) {
+  if (tr && !tr->has_intervals && !tr->traverse_unplaced_unmapped)
+    RET(DQ_EINVAL, "Traversing mapped reads only is not supported.");
+  if (int rc0 = check_tail_reachable(ctx, tr)) return rc0;
+  int rc = run_pipeline(ctx);
+  if (rc) return rc;
+  bounds.assign(1, 0);
+  int64_t total = 0;
+  for (size_t i = 0; i < ctx->plans_h.size(); i++) {
+    const SplitPlan& P = ctx->plans_h[i];
+    if (P.rec_lin < 0) continue;  // empty partition (no PathChunk)
+    const PartRange& r = ctx->parts_h[i];
+    if (!tr) {
+      ranges.push_back({r.begin, r.end});
+      total += r.end - r.begin;
+    } else {
+      std::vector<int64_t> f;
+      if ((rc = filtered_indices(ctx, P.vstart, P.vend, r.begin, r.end, tr, f))) return rc;
+      idx.insert(idx.end(), f.begin(), f.end());
+      total = (int64_t)idx.size();
+    }
+    bounds.push_back(total);
+  }
+  return 0;
+}
+
 extern "C" {
 
 const char* dq_version(void) { return "disq_amd 0.2 (gfx950)"; }
@@ -3486,29 +3523,10 @@ int dq_decode_filtered(dq_ctx* ctx, uint64_t vstart, uint64_t vend, const dq_tra
 int dq_read(dq_ctx* ctx, const dq_traversal* tr, int32_t with_raw, dq_batch** out) {
   if (!ctx || !out) return DQ_EINVAL;
   ON_DEVICE(ctx);
-  if (tr && !tr->has_intervals && !tr->traverse_unplaced_unmapped)
-    RET(DQ_EINVAL, "Traversing mapped reads only is not supported.");
-  if (int rc0 = check_tail_reachable(ctx, tr)) return rc0;
-  int rc = run_pipeline(ctx);
-  if (rc) return rc;
-  std::vector<int64_t> idx, bounds{0};
+  std::vector<int64_t> idx, bounds;
   std::vector<std::pair<int64_t, int64_t>> ranges;
-  int64_t total = 0;
-  for (size_t i = 0; i < ctx->plans_h.size(); i++) {
-    const SplitPlan& P = ctx->plans_h[i];
-    if (P.rec_lin < 0) continue;  // empty partition (no PathChunk)
-    const PartRange& r = ctx->parts_h[i];
-    if (!tr) {
-      ranges.push_back({r.begin, r.end});
-      total += r.end - r.begin;
-    } else {
-      std::vector<int64_t> f;
-      if ((rc = filtered_indices(ctx, P.vstart, P.vend, r.begin, r.end, tr, f))) return rc;
-      idx.insert(idx.end(), f.begin(), f.end());
-      total = (int64_t)idx.size();
-    }
-    bounds.push_back(total);
-  }
+  int rc = read_rows(ctx, tr, ranges, idx, bounds);
+  if (rc) return rc;
   if (!tr) {
     // a single range is copied straight from the resident arrays (ranges.size() <= 1)
     return make_batch(ctx, ranges, nullptr, with_raw, bounds, out);
@@ -4626,6 +4644,194 @@ void dq_info_batch_free(dq_info_batch* b) {
   free(b);
 }
 
+// ---- BAM aux tag decode (row f12): the optional fields of dq_read's (dq_sam_read's) rows projected
+// onto the caller's keys.  The check and decode passes of dq_tags.hip run on
+// the columns the records stage left in HBM; the tag columns stay there too.
+static int tags_run(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t n_keys) {
+  if (ctx->text_mode && !ctx->sam_mode) RET(DQ_EINVAL, "a text (VCF) context holds no records");
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  if (ctx->sam_mode && tr) RET(DQ_EINVAL, "dq_tags: a SAM context takes no traversal");
+  if (!keys || n_keys < 1 || n_keys > dqa::TAG_MAX_KEYS) RET(DQ_EINVAL, "dq_tags: 1 to 64 keys are taken");
+  struct {
+    uint32_t slot[dqa::TAG_SLOTS];
+    uint8_t type[64];
+  } kt{};
+  std::vector<const char*> ids;
+  std::vector<int32_t> types;
+  for (int32_t q = 0; q < n_keys; q++) {
+    ids.push_back(keys[q].id);
+    types.push_back(keys[q].type);
+  }
+  if (const char* why = dqa::tag_keys_build(ids.data(), types.data(), n_keys, kt.slot, kt.type))
+    RET(DQ_EINVAL, std::string("dq_tags: ") + why);
+  // ---- the rows
+  int rc;
+  std::vector<int64_t> idx, bounds;
+  std::vector<std::pair<int64_t, int64_t>> ranges, runs;
+  int64_t src_len = 0;
+  if (ctx->sam_mode) {
+    if ((rc = sam_run(ctx))) return rc;
+    bounds.assign(1, 0);
+    for (const PartRange& r : ctx->parts_h) {
+      ranges.push_back({r.begin, r.end});
+      bounds.push_back(bounds.back() + (r.end - r.begin));
+    }
+    if (ctx->nrec > 0 && (rc = get_i64(ctx, ctx->rec_lin.as<int64_t>() + ctx->nrec, &src_len))) return rc;
+  } else {
+    if ((rc = read_rows(ctx, tr, ranges, idx, bounds))) return rc;
+    src_len = ctx->ulen;
+  }
+  if (!tr) {  // adjacent ranges form one run of the resident arrays, as make_batch joins them
+    for (auto& r : ranges) {
+      if (r.second <= r.first) continue;
+      if (!runs.empty() && runs.back().second == r.first) runs.back().second = r.second;
+      else runs.push_back(r);
+    }
+    if (runs.size() > 1)
+      for (auto& r : runs)
+        for (int64_t k = r.first; k < r.second; k++) idx.push_back(k);
+  }
+  const bool listed = tr || runs.size() > 1;
+  const int64_t n = listed ? (int64_t)idx.size() : runs.empty() ? 0 : runs[0].second - runs[0].first;
+  const int64_t first = listed || runs.empty() ? 0 : runs[0].first;
+  if (n != bounds.back()) RET(DQ_EDEVICE, "dq_tags: the row list and the partitions' bounds differ");
+  hipStream_t s = ctx->s;
+  const int64_t K = n_keys;
+  if ((rc = ensure_all(ctx, ctx->a_keys, sizeof kt)) || (rc = ensure_all(ctx, ctx->a_scal, 64)) ||
+      (rc = ensure_all(ctx, ctx->a_base, 8 * 64)) ||
+      (rc = ensure_all(ctx, ctx->a_idx, 8 * (size_t)std::max<int64_t>(1, listed ? n : 0))))
+    return rc;
+  HIPCHK(hipMemcpy(ctx->a_keys.p, &kt, sizeof kt, hipMemcpyHostToDevice));
+  if (listed && n > 0) HIPCHK(hipMemcpy(ctx->a_idx.p, idx.data(), 8 * (size_t)n, hipMemcpyHostToDevice));
+  const RecSoA soa = ctx->soa();
+  const dq::TagIn in{ctx->rec_src(), src_len, ctx->rec_lin.as<int64_t>(), soa.block_size, soa.l_seq, soa.n_cigar,
+                     soa.l_read_name, ctx->nrec, listed ? ctx->a_idx.as<int64_t>() : nullptr, first, n,
+                     ctx->a_keys.as<uint32_t>(), ctx->a_keys.as<uint8_t>() + sizeof kt.slot, n_keys};
+  // ---- check: the first failing (row, check)
+  unsigned long long* d_scal = ctx->a_scal.as<unsigned long long>();
+  unsigned long long sc = ~0ull;
+  HIPCHK(hipMemcpy(d_scal, &sc, 8, hipMemcpyHostToDevice));
+  HIPCHK(hipEventRecord(ctx->ev[20], s));
+  dq::launch_tags_check(in, d_scal, s);
+  HIPCHK(hipEventRecord(ctx->ev[21], s));
+  HIPCHK(hipMemcpyAsync(&sc, d_scal, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (sc != ~0ull) {
+    char nb[16];
+    RET(DQ_EFORMAT, "record " + std::to_string((long long)(sc >> 20)) + ": " +
+                        dqa::tag_error_name((int32_t)(sc & 0xfffff), nb));
+  }
+  // ---- the columns' shapes: a value block of n cells per INT, FLOAT or CHAR key
+  std::vector<int64_t> base((size_t)K, -1);
+  int64_t nval = 0;
+  for (int64_t q = 0; q < K; q++) {
+    const int32_t ty = types[(size_t)q];
+    if (ty != dqa::TAG_INT && ty != dqa::TAG_FLOAT && ty != dqa::TAG_CHAR) continue;
+    base[(size_t)q] = nval;
+    nval += n;
+  }
+  HIPCHK(hipMemcpy(ctx->a_base.p, base.data(), 8 * (size_t)K, hipMemcpyHostToDevice));
+  const size_t cells = (size_t)K * (size_t)n;
+  const char* nomem = "the tag columns do not fit in device memory";
+  const auto ensure8 = [&](DevBuf& b, size_t bytes) { return ensure_or_nomem(ctx, b, std::max<size_t>(8, bytes), nomem); };
+  if ((rc = ensure8(ctx->a_flags, cells)) || (rc = ensure8(ctx->a_vtype, cells)) || (rc = ensure8(ctx->a_sub, cells)) ||
+      (rc = ensure8(ctx->a_off, 4 * cells)) || (rc = ensure8(ctx->a_len, 4 * cells)) ||
+      (rc = ensure8(ctx->a_val, 4 * (size_t)nval)))
+    return rc;
+  const dq::TagCols out{ctx->a_flags.as<uint8_t>(), ctx->a_vtype.as<uint8_t>(), ctx->a_sub.as<uint8_t>(),
+                        ctx->a_off.as<int32_t>(),   ctx->a_len.as<int32_t>(),   ctx->a_val.as<uint32_t>(),
+                        nval,                       ctx->a_base.as<int64_t>()};
+  HIPCHK(hipEventRecord(ctx->ev[22], s));
+  dq::launch_tags_decode(in, out, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ev[23], s));
+  HIPCHK(hipStreamSynchronize(s));
+  ctx->tag_n = n;
+  ctx->tag_nval = nval;
+  ctx->tag_type = types;
+  ctx->tag_base = base;
+  ctx->tag_bounds = bounds;
+  ctx->tag_ms = n > 0 ? (double)ev_ms(ctx->ev[20], ctx->ev[21]) + (double)ev_ms(ctx->ev[22], ctx->ev[23]) : 0.0;
+  return 0;
+}
+
+int dq_tags_run(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t n_keys, dq_stats* stats) {
+  if (!ctx) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  int rc = tags_run(ctx, tr, keys, n_keys);
+  if (rc) return rc;
+  if (stats) {
+    *stats = ctx->stats;
+    stats->ms_records += ctx->tag_ms;
+    stats->ms_total += ctx->tag_ms;
+  }
+  return 0;
+}
+
+int dq_tags(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t n_keys, dq_tag_batch** out) {
+  if (!ctx || !out) return DQ_EINVAL;
+  ON_DEVICE(ctx);
+  *out = nullptr;
+  int rc = tags_run(ctx, tr, keys, n_keys);
+  if (rc) return rc;
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->tag_n, np = (int64_t)ctx->tag_bounds.size() - 1;
+  const size_t K = (size_t)n_keys, cells = K * (size_t)n, c1 = std::max<size_t>(1, cells);
+  const size_t nval = (size_t)ctx->tag_nval;
+  dq_tag_batch* b = (dq_tag_batch*)calloc(1, sizeof(dq_tag_batch));
+  if (!b) return DQ_ENOMEM;
+  b->n_records = n;
+  b->n_keys = n_keys;
+  b->key_type = (int32_t*)malloc(4 * K);
+  b->key_base = (int64_t*)malloc(8 * K);
+  b->flags = (uint8_t*)malloc(c1);
+  b->vtype = (uint8_t*)malloc(c1);
+  b->subtype = (uint8_t*)malloc(c1);
+  b->val_off = (int32_t*)malloc(4 * c1);
+  b->val_len = (int32_t*)malloc(4 * c1);
+  b->val = (uint32_t*)malloc(4 * std::max<size_t>(1, nval));
+  b->n_val = (int64_t)nval;
+  b->n_partitions = np;
+  b->part_offset = (int64_t*)malloc(8 * (size_t)(np + 1));
+  if (!(b->key_type && b->key_base && b->flags && b->vtype && b->subtype && b->val_off && b->val_len && b->val &&
+        b->part_offset)) {
+    dq_tag_batch_free(b);
+    return DQ_ENOMEM;
+  }
+  memcpy(b->key_type, ctx->tag_type.data(), 4 * K);
+  memcpy(b->key_base, ctx->tag_base.data(), 8 * K);
+  memcpy(b->part_offset, ctx->tag_bounds.data(), 8 * (size_t)(np + 1));
+  if (cells > 0) {
+    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
+        {b->flags, ctx->a_flags.p, cells},       {b->vtype, ctx->a_vtype.p, cells},
+        {b->subtype, ctx->a_sub.p, cells},       {b->val_off, ctx->a_off.p, 4 * cells},
+        {b->val_len, ctx->a_len.p, 4 * cells},   {b->val, ctx->a_val.p, 4 * nval}};
+    bool ok = true;
+    for (const auto& c : cp)
+      if (c.bytes) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
+      dq_tag_batch_free(b);
+      RET(DQ_EDEVICE, "dq_tags: device to host copy failed");
+    }
+  }
+  *out = b;
+  return 0;
+}
+
+void dq_tag_batch_free(dq_tag_batch* b) {
+  if (!b) return;
+  free(b->key_type);
+  free(b->key_base);
+  free(b->flags);
+  free(b->vtype);
+  free(b->subtype);
+  free(b->val_off);
+  free(b->val_len);
+  free(b->val);
+  free(b->part_offset);
+  free(b);
+}
+
 // TabixIndexCreator / BinningIndexBuilder (DESIGN.md "Building the .tbi"): data lines, their keys
 // and runs on the device (dq_text.hip), then the .bai kernels over the same key / voff / endp / pos
 // arrays; the host names the contigs, orders the bin headers and serialises.
@@ -4988,11 +5194,12 @@ int dq_checked_report(uint64_t words[4]) {
       words[2] = cnt << 32 | ex << 16 | ((a | b) & 0xffff);
     }
   }
-  for (int u = 0; u < 4; u++) {  // and so do the SAM writer's unit and the VCF decodes' three
+  for (int u = 0; u < 5; u++) {  // and so do the SAM writer's unit, the VCF decodes' three and the tags'
     const uint64_t a = words[2], b = u == 0   ? dq::dq_chk_take_samw()
                                      : u == 1 ? dq::dq_chk_take_vcf()
                                      : u == 2 ? dq::dq_chk_take_vcfgt()
-                                              : dq::dq_chk_take_vcfinfo();
+                                     : u == 3 ? dq::dq_chk_take_vcfinfo()
+                                              : dq::dq_chk_take_tags();
     if (a == ~0ull || b == ~0ull) {
       words[2] = ~0ull;
     } else {

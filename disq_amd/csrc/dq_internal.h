@@ -47,8 +47,9 @@ enum : int {
   CHK_K3_SPEC = 13,  // K3: the LDS-filtered segment speculation differs from seg_spec_kernel<64>
   CHK_BAI = 14,      // .bai build: a linear window, perm slot, chunk or bin outside its table
   CHK_TBI = 15,      // .tbi build: a data-line slot, block, run or name byte outside its table
-  CHK_SAM = 15,      // SAM read and write (dq_sam.hip, dq_samw.hip share the bit): a line, size,
-                     //     record-byte, line-byte or fix-up slot
+  CHK_SAM = 15,      // SAM read and write and the tag decode (dq_sam.hip, dq_samw.hip, dq_tags.hip share
+                     //     the bit): a line, size, record-byte, line-byte or fix-up slot; a tag row,
+                     //     key or value slot
   CHK_VCF = 15,      // VCF site, genotype and INFO decode (dq_vcf.hip, dq_vcf_gt.hip, dq_vcf_info.hip
                      //     share the bit): a line, column row, matrix or INFO cell, LDS offset slot,
                      //     fix-up slot or site byte
@@ -541,12 +542,44 @@ void launch_samw_format(const uint8_t* raw, int64_t raw_len, const int64_t* off,
                         SamwRefs refs, const int64_t* loff, uint8_t* text, int32_t use_tile,
                         hipStream_t s);
 
+// ------------------------------------------------------------------ BAM aux tag decode (dq_tags.hip)
+struct TagIn {              // row j is record idx[j] (idx == nullptr: first + j) of the nrec resident ones
+  const uint8_t* src;       // the records' bytes: record k at src[rec_lin[k]], src_len readable
+  int64_t src_len;
+  const int64_t* rec_lin;
+  const int32_t* block_size;
+  const int32_t* l_seq;
+  const uint16_t* n_cigar;
+  const uint8_t* l_read_name;
+  int64_t nrec;
+  const int64_t* idx;
+  int64_t first, n;
+  const uint32_t* key_slot; // dqa::TagKeys in device memory (dq_tags_core.h): TAG_SLOTS slots, n_keys types
+  const uint8_t* key_type;
+  int32_t n_keys;
+};
+struct TagCols {            // the arrays of dq_tag_batch, key-major: cell (q, k) at q * n + k
+  uint8_t* flags;
+  uint8_t* vtype;
+  uint8_t* subtype;
+  int32_t* val_off;
+  int32_t* val_len;
+  uint32_t* val;
+  int64_t n_val;
+  const int64_t* key_base;  // [K] in device memory
+};
+// Check pass: scal[0] (all ones) takes the smallest dqa::tag_error_key.
+void launch_tags_check(TagIn in, unsigned long long* scal, hipStream_t s);
+// Decode pass: every cell of the K x n columns.
+void launch_tags_decode(TagIn in, TagCols out, hipStream_t s);
+
 // DQ_CHECKED: each kernel unit's check words (count << 32 | site bits), read and reset
 uint64_t dq_chk_take_sam();
 uint64_t dq_chk_take_samw();
 uint64_t dq_chk_take_vcf();
 uint64_t dq_chk_take_vcfgt();
 uint64_t dq_chk_take_vcfinfo();
+uint64_t dq_chk_take_tags();
 uint64_t dq_chk_take_kernels();
 uint64_t dq_chk_take_inflate();
 uint64_t dq_chk_take_text();

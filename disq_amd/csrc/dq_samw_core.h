@@ -7,12 +7,14 @@
 //
 // One walk serves both passes: with out == nullptr it validates and sizes the line, with out set it
 // writes the bytes, every store bounded by the size the first pass gave; so a line can never get
-// more bytes than it was sized for.
+// more bytes than it was sized for.  The tag chain is stepped through with dq_tags_core.h's tag_next,
+// which the tag decode (dq_tags.hip) shares.
 #pragma once
 #include <stdint.h>
 
 #include "dq_sam_core.h"
 #include "dq_samw_pow5.h"
+#include "dq_tags_core.h"
 
 namespace dqw {
 
@@ -451,87 +453,66 @@ DQT_INLINE int32_t samw_record_walk(const uint8_t* r, int64_t avail, const RefNa
   } else {
     for (int32_t i = 0; i < n; i++) put(s, (uint8_t)(ql[i] + 33));
   }
-  // ---- tags, in stored order
+  // ---- tags, in stored order (dq_tags_core.h locates and validates each one)
   int64_t p = L.tags_at;
   const int64_t end = L.end;
   while (p < end) {
-    if (end - p < 3) return dqs::sam_tag_error(r + p, 0);
-    const int32_t err = dqs::sam_tag_error(r + p, 2);
-    const uint8_t ty = r[p + 2];
+    dqa::Tag T;
+    const int32_t err = dqa::tag_next(r, p, end, &T);
+    if (err) return err;
+    const uint8_t ty = T.ty;
+    const uint8_t* v = r + T.at;
     put(s, '\t');
     put(s, r[p]);
     put(s, r[p + 1]);
     put(s, ':');
-    p += 3;
-    const int64_t left = end - p;
     if (ty == 'A') {
-      if (left < 1) return err;
       put(s, 'A');
       put(s, ':');
-      put(s, r[p]);
-      p += 1;
-    } else if (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I') {
-      const int sz = (ty == 'c' || ty == 'C') ? 1 : (ty == 's' || ty == 'S') ? 2 : 4;
-      if (left < sz) return err;
-      put(s, 'i');
-      put(s, ':');
-      if (ty == 'c') put_i32(s, (int8_t)r[p]);
-      else if (ty == 'C') put_u32(s, r[p]);
-      else if (ty == 's') put_i32(s, (int16_t)rd16(r + p));
-      else if (ty == 'S') put_u32(s, rd16(r + p));
-      else if (ty == 'i') put_i32(s, rd32(r + p));
-      else put_u32(s, (uint32_t)rd32(r + p));
-      p += sz;
+      put(s, v[0]);
     } else if (ty == 'f') {
-      if (left < 4) return err;
       put(s, 'f');
       put(s, ':');
-      put_float(s, (uint32_t)rd32(r + p));
-      p += 4;
+      put_float(s, (uint32_t)rd32(v));
     } else if (ty == 'Z' || ty == 'H') {
-      int64_t z = p;
-      while (z < end && r[z] != 0) z++;
-      if (z >= end) return err;
       put(s, ty);
       put(s, ':');
       if (ty == 'Z') {
-        put_bytes(s, r + p, z - p);
+        put_bytes(s, v, T.len);
       } else {
-        if ((z - p) & 1) return err;
-        for (int64_t i = p; i < z; i++) {
-          const uint8_t c = r[i];
-          const bool lower = c >= 'a' && c <= 'f';
-          if (!(lower || (c >= 'A' && c <= 'F') || (c >= '0' && c <= '9'))) return err;
-          put(s, lower ? (uint8_t)(c - 32) : c);
+        for (int64_t i = 0; i < T.len; i++) {
+          const uint8_t c = v[i];
+          put(s, c >= 'a' && c <= 'f' ? (uint8_t)(c - 32) : c);
         }
       }
-      p = z + 1;
     } else if (ty == 'B') {
-      if (left < 5) return err;
-      const uint8_t sub = r[p];
-      const int32_t cnt = rd32(r + p + 1);
-      p += 5;
-      const int sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 :
-                     (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-      if (sz == 0 || cnt < 0 || (int64_t)sz * cnt > end - p) return err;
+      const uint8_t sub = T.sub;
+      const int sz = sub == 'f' ? 4 : dqa::tag_int_size(sub);
       put(s, 'B');
       put(s, ':');
       put(s, sub);
-      for (int32_t k = 0; k < cnt; k++) {
-        const uint8_t* v = r + p + (int64_t)sz * k;
+      for (int32_t k = 0; k < T.count; k++) {
+        const uint8_t* e = v + (int64_t)sz * k;
         put(s, ',');
-        if (sub == 'c') put_i32(s, (int8_t)v[0]);
-        else if (sub == 'C') put_u32(s, v[0]);
-        else if (sub == 's') put_i32(s, (int16_t)rd16(v));
-        else if (sub == 'S') put_u32(s, rd16(v));
-        else if (sub == 'i') put_i32(s, rd32(v));
-        else if (sub == 'I') put_u32(s, (uint32_t)rd32(v));
-        else put_float(s, (uint32_t)rd32(v));
+        if (sub == 'c') put_i32(s, (int8_t)e[0]);
+        else if (sub == 'C') put_u32(s, e[0]);
+        else if (sub == 's') put_i32(s, (int16_t)rd16(e));
+        else if (sub == 'S') put_u32(s, rd16(e));
+        else if (sub == 'i') put_i32(s, rd32(e));
+        else if (sub == 'I') put_u32(s, (uint32_t)rd32(e));
+        else put_float(s, (uint32_t)rd32(e));
       }
-      p += (int64_t)sz * cnt;
-    } else {
-      return err;
+    } else {  // c C s S i I: tag_next knows no other type
+      put(s, 'i');
+      put(s, ':');
+      if (ty == 'c') put_i32(s, (int8_t)v[0]);
+      else if (ty == 'C') put_u32(s, v[0]);
+      else if (ty == 's') put_i32(s, (int16_t)rd16(v));
+      else if (ty == 'S') put_u32(s, rd16(v));
+      else if (ty == 'i') put_i32(s, rd32(v));
+      else put_u32(s, (uint32_t)rd32(v));
     }
+    p = T.next;
   }
   // String.trim has cut the line at `keep`; saveAsTextFile's LF follows
   W->size = s.keep + 1;

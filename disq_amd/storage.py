@@ -81,6 +81,7 @@ class ReadsPartition:
     raw: Optional[np.ndarray]
     digest: int
     path: str = ""
+    tags: Optional[dict] = None  # read(tags=...): per requested id the partition's tag columns
 
     def __len__(self):
         return len(self.fields["voffset"])
@@ -107,6 +108,20 @@ class ReadsRDD:
 
     def hashes(self):
         return self.field("hash").astype(np.uint64)
+
+    def tag(self, name):
+        """The columns of one of the tags asked of read(tags=[...]), per partition: a list of dicts
+        with flags, vtype, subtype, val_off, val_len (one entry per read; val_off counts from the
+        read's block_size word, so it indexes record_bytes(i)) and values (Context.tags' typed
+        view of the key, None for an ANY or STRING key).  KeyError for a tag that was not asked
+        for."""
+        name = name.decode() if isinstance(name, bytes) else name
+        out = []
+        for p in self.partitions:
+            if p.tags is None or name not in p.tags:
+                raise KeyError(name)
+            out.append(p.tags[name])
+        return out
 
 
 class HtsjdkReadsRdd:
@@ -192,8 +207,10 @@ class HtsjdkReadsRddStorage:
             return [os.path.join(path, n) for n in names]
         return [path]
 
-    def read(self, path: str, traversalParameters: Optional[HtsjdkReadsTraversalParameters] = None
-             ) -> HtsjdkReadsRdd:
+    def read(self, path: str, traversalParameters: Optional[HtsjdkReadsTraversalParameters] = None,
+             tags: Optional[Sequence] = None) -> HtsjdkReadsRdd:
+        """tags (extension): aux tag ids, or (id, _lib.TAG_* class) pairs, decoded on the device
+        next to the reads (Context.tags) and handed out per partition by ReadsRDD.tag(id)."""
         files = self._files(path)
         if not files:
             raise ValueError(f"No files found in {path}")
@@ -248,8 +265,18 @@ class HtsjdkReadsRddStorage:
                     trav = (conv, tp.getTraverseUnplacedUnmapped())
                 b = ctx.sam_read(with_raw=True) if sam else ctx.read(with_raw=True, traversal=trav)
                 po = b["part_offset"]
+                g = ctx.tags(list(tags), traversal=trav) if tags else None
+                if g is not None and g["part_offset"].tolist() != po.tolist():
+                    raise RuntimeError("the tag columns' partitions differ from the reads'")
                 for p in range(len(po) - 1):
                     lo, hi = int(po[p]), int(po[p + 1])
+                    ptags = None
+                    if g is not None:
+                        ptags = {}
+                        for q, vid in enumerate(g["keys"]):
+                            t = {k: g[k][q, lo:hi] for k in ("flags", "vtype", "subtype", "val_off", "val_len")}
+                            t["values"] = None if g["values"][q] is None else g["values"][q][lo:hi]
+                            ptags[vid.decode()] = t
                     fields = {k: b[k][lo:hi] for k, _ in _lib.FIELDS}
                     raw = None
                     if b["raw"] is not None and hi > lo:
@@ -257,7 +284,7 @@ class HtsjdkReadsRddStorage:
                         r1 = int(fields["raw_offset"][-1]) + 4 + int(fields["block_size"][-1])
                         raw = b["raw"][r0:r1]
                         fields["raw_offset"] = fields["raw_offset"] - r0
-                    parts.append(ReadsPartition(fields, raw, int(b["part_digest"][p]), f))
+                    parts.append(ReadsPartition(fields, raw, int(b["part_digest"][p]), f, ptags))
         return HtsjdkReadsRdd(header, ReadsRDD(parts))
 
     def write(self, rdd: HtsjdkReadsRdd, path: str, tempPartsDirectory: Optional[str] = None, *,

@@ -614,6 +614,64 @@ int dq_sam_write(dq_ctx* ctx, const uint8_t* header, int64_t header_len, const u
 int dq_sam_write_resident(dq_ctx* ctx, int64_t* out_len, double* ms);
 int dq_sam_write_fetch(dq_ctx* ctx, uint8_t* host_out, int64_t cap);
 
+/* ---- BAM aux tags projected onto keys -------------------------
+ * The optional fields (SAMv1 section 4.2.4) of the records dq_read(ctx, tr, ...) returns on a BAM
+ * context -- the same records in the same order and partitions, whether tr is NULL, carries
+ * intervals or asks for the unplaced tail, the records DQ_COMPAT_DISQ_EXACT duplicates across a
+ * split boundary included, a shard its own partitions -- or of dq_sam_read's on a SAM context (tr
+ * must be NULL), decoded on the device into one column block per requested key (1 to 64 keys): what
+ * SAMRecord.getAttribute reads for those keys.  The rules are DESIGN.md section 18.  A record's aux
+ * region runs from 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq to 4 + block_size; a
+ * layout that does not fit is the SAM writer's "fields".  The whole chain is walked and validated
+ * with the SAM writer's checks (the bytes a type needs are left in the record, Z and H end in a
+ * NUL, H is an even number of hex digits, a B array's element type and count, the type byte is
+ * known).  An id is two bytes, [A-Za-z][A-Za-z0-9], matched byte for byte; the first occurrence of
+ * a key in a record is decoded and a later one only sets DQ_TAG_REPEATED.
+ * Errors: the first failing check of the lowest row, in stored order, gives DQ_EFORMAT and
+ * dq_last_error "record <k>: fields", "record <k>: tag XX" (XX as dq_sam_write names it; no name
+ * when fewer than three bytes are left) or "record <k>: tag XX type" (a requested key whose first
+ * occurrence is stored outside the class asked for); k is the 0-based row.  DQ_EINVAL: a text (VCF)
+ * context, no open file, tr on a SAM context, n_keys < 1 or > 64, a bad id, the same id twice, an
+ * unknown type, and what dq_read refuses.  DQ_ENOMEM: the columns do not fit.  dq_read,
+ * dq_sam_read, dq_write_bai and dq_sam_write_resident work on the same context afterwards.
+ * Not done: dense values of B arrays and copies of Z/H text (reached through the span); htsjdk's
+ * rule for a tag stored twice in one record is not reproduced (its tag codec's source was not at
+ * hand to check it against: here the first occurrence wins and the cell says so); the chunk calls
+ * (dq_decode_chunk*), multi-GPU wiring and CRAM. */
+#define DQ_TAG_ANY 0     /* any stored type: vtype, subtype and span only, nothing converted */
+#define DQ_TAG_INT 1     /* stored c C s S i I  (getIntegerAttribute and friends) */
+#define DQ_TAG_FLOAT 2   /* stored f */
+#define DQ_TAG_CHAR 3    /* stored A */
+#define DQ_TAG_STRING 4  /* stored Z: the span is the access path */
+/* cell flags */
+#define DQ_TAG_PRESENT 1
+#define DQ_TAG_REPEATED 4   /* the tag occurs again later in the record; the first is decoded */
+typedef struct dq_tag_key { const char* id; int32_t type; int32_t reserved; } dq_tag_key;
+typedef struct dq_tag_batch {
+  int64_t n_records;      /* = the batch of dq_read (dq_sam_read); row k is its record k */
+  int32_t n_keys;         /* K, 1..64 */
+  int32_t reserved;
+  int32_t* key_type;      /* [K] as asked */
+  int64_t* key_base;      /* [K] element offset of key q's block in val (INT, FLOAT, CHAR), else -1 */
+  uint8_t* flags;         /* [K * n], key-major: cell (q, k) at q * n + k */
+  uint8_t* vtype;         /* [K * n] stored type byte (A c C s S i I f Z H B), 0 when absent */
+  uint8_t* subtype;       /* [K * n] element type of a B array, else 0 */
+  int32_t* val_off;       /* [K * n] offset of the value's first payload byte in the record, counted
+                             from its block_size word (so raw[raw_offset[k] + val_off]); -1 absent.
+                             Z/H: first character; B: first element, behind subtype and count */
+  int32_t* val_len;       /* [K * n] payload bytes: Z/H without the NUL, B = element size * count */
+  uint32_t* val; int64_t n_val; /* cell (q, k) at key_base[q] + k: INT the value extended to 32 bits as
+                             its stored type says (for 'I' the uint32 itself; vtype tells), FLOAT the
+                             binary32 bits, CHAR the byte; 0 when absent */
+  int64_t n_partitions; int64_t* part_offset;   /* as the record batch */
+} dq_tag_batch;
+/* The pipeline as dq_read (dq_sam_read) runs it, then the tag check and decode passes for these
+ * keys; the columns stay in HBM.  stats: the pipeline's, with the device time of the two tag passes
+ * added to ms_records and to ms_total. */
+int dq_tags_run(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t n_keys, dq_stats* stats);
+int dq_tags(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t n_keys, dq_tag_batch** out);
+void dq_tag_batch_free(dq_tag_batch* b);
+
 /* ---- BGZF compression: the write path -----------------------
  * Replaces htsjdk BlockCompressedOutputStream under HeaderlessBamOutputFormat.BamRecordWriter
  * (D/impl/formats/bam/HeaderlessBamOutputFormat.java:26-50) and BamSink's header file
@@ -645,7 +703,7 @@ void dq_free(void* p);
 /* Debug: the device bounds-checked build (`make -C disq_amd/csrc checked` ->
  * libdisq_gpu_checked.so, compiled with -DDQ_CHECKED).  Writes each kernel unit's failed-check
  * count << 32 | largest reported excess << 16 | site bits (K1/K3 kernels, K2 inflate, text
- * with the SAM reader's and writer's units folded in, deflate: 4 words) for the current
+ * with the SAM reader's, the SAM writer's and the tag decode's units folded in, deflate: 4 words) for the current
  * device and resets them; returns 1 in the checked build, 0 in the product build (words all 0). */
 int dq_checked_report(uint64_t words[4]);
 
