@@ -322,6 +322,20 @@ def check(ctx, rc):
     return rc
 
 
+def _arr(ptr, k, dt):
+    """A copy of the k elements at a batch's pointer (empty for none or a null pointer)."""
+    if not k or not ptr:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
+
+
+def _name_list(off_ptr, bytes_ptr, n):
+    """The n names a batch packs as n + 1 int32 offsets into one byte array, as bytes objects."""
+    no = _arr(off_ptr, n + 1, np.int32)
+    names = _arr(bytes_ptr, int(no[-1]) if len(no) else 0, np.uint8).tobytes()
+    return [names[no[i]:no[i + 1]] for i in range(n)]
+
+
 FIELDS = (("voffset", np.uint64), ("block_size", np.int32), ("ref_id", np.int32),
           ("pos", np.int32), ("l_seq", np.int32), ("next_ref_id", np.int32),
           ("next_pos", np.int32), ("tlen", np.int32), ("flag", np.uint16), ("bin", np.uint16),
@@ -607,18 +621,13 @@ class Context:
         try:
             b = bp.contents
             n, npart = b.n_lines, b.n_partitions
-
-            def arr(ptr, k, dt):
-                if not k or not ptr:
-                    return np.zeros(0, dt)
-                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
-            return {"line_offset": arr(b.line_offset, n, np.int64),
-                    "line_len": arr(b.line_len, n, np.int32),
-                    "hash": arr(b.hash, n, np.uint64),
-                    "data_offset": arr(b.data_offset, n + 1, np.int64),
-                    "data": arr(b.data, b.n_bytes, np.uint8),
-                    "part_offset": arr(b.part_offset, npart + 1, np.int64),
-                    "part_digest": arr(b.part_digest, npart, np.uint64)}
+            return {"line_offset": _arr(b.line_offset, n, np.int64),
+                    "line_len": _arr(b.line_len, n, np.int32),
+                    "hash": _arr(b.hash, n, np.uint64),
+                    "data_offset": _arr(b.data_offset, n + 1, np.int64),
+                    "data": _arr(b.data, b.n_bytes, np.uint8),
+                    "part_offset": _arr(b.part_offset, npart + 1, np.int64),
+                    "part_digest": _arr(b.part_digest, npart, np.uint64)}
         finally:
             lib().dq_text_batch_free(bp)
 
@@ -641,30 +650,22 @@ class Context:
         try:
             b = bp.contents
             n, npart = b.n_variants, b.n_partitions
-
-            def arr(ptr, k, dt):
-                if not k or not ptr:
-                    return np.zeros(0, dt)
-                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
-            no = arr(b.contig_name_off, b.n_contigs + 1, np.int32)
-            names = arr(b.contig_names, int(no[-1]) if len(no) else 0, np.uint8).tobytes()
-            out = {"line_offset": arr(b.line_offset, n, np.int64),
-                   "line_len": arr(b.line_len, n, np.int32),
-                   "hash": arr(b.hash, n, np.uint64),
-                   "contig": arr(b.contig, n, np.int32), "pos": arr(b.pos, n, np.int32),
-                   "end": arr(b.end, n, np.int32), "flags": arr(b.flags, n, np.uint32),
-                   "qual": arr(b.qual, n, np.float64),
-                   "col_end": arr(b.col_end, 8 * n, np.int32).reshape(-1, 8),
-                   "n_alt": arr(b.n_alt, n, np.int32), "n_filter": arr(b.n_filter, n, np.int32),
-                   "n_info": arr(b.n_info, n, np.int32),
-                   "n_sample_cols": arr(b.n_sample_cols, n, np.int32),
-                   "data_offset": arr(b.data_offset, n + 1, np.int64),
-                   "data": arr(b.data, b.n_bytes, np.uint8),
-                   "part_offset": arr(b.part_offset, npart + 1, np.int64),
-                   "part_digest": arr(b.part_digest, npart, np.uint64),
-                   "contigs": [names[no[i]:no[i + 1]] for i in range(b.n_contigs)],
-                   "n_bytes": int(b.n_bytes), "n_qual_host": int(b.n_qual_host)}
-            return out
+            return {"line_offset": _arr(b.line_offset, n, np.int64),
+                    "line_len": _arr(b.line_len, n, np.int32),
+                    "hash": _arr(b.hash, n, np.uint64),
+                    "contig": _arr(b.contig, n, np.int32), "pos": _arr(b.pos, n, np.int32),
+                    "end": _arr(b.end, n, np.int32), "flags": _arr(b.flags, n, np.uint32),
+                    "qual": _arr(b.qual, n, np.float64),
+                    "col_end": _arr(b.col_end, 8 * n, np.int32).reshape(-1, 8),
+                    "n_alt": _arr(b.n_alt, n, np.int32), "n_filter": _arr(b.n_filter, n, np.int32),
+                    "n_info": _arr(b.n_info, n, np.int32),
+                    "n_sample_cols": _arr(b.n_sample_cols, n, np.int32),
+                    "data_offset": _arr(b.data_offset, n + 1, np.int64),
+                    "data": _arr(b.data, b.n_bytes, np.uint8),
+                    "part_offset": _arr(b.part_offset, npart + 1, np.int64),
+                    "part_digest": _arr(b.part_digest, npart, np.uint64),
+                    "contigs": _name_list(b.contig_name_off, b.contig_names, b.n_contigs),
+                    "n_bytes": int(b.n_bytes), "n_qual_host": int(b.n_qual_host)}
         finally:
             lib().dq_variant_batch_free(bp)
 
@@ -686,21 +687,14 @@ class Context:
         try:
             b = bp.contents
             n, S, P = b.n_variants, b.n_samples, b.max_ploidy
-
-            def arr(ptr, k, dt):
-                if not k or not ptr:
-                    return np.zeros(0, dt)
-                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
-            no = arr(b.sample_name_off, S + 1, np.int32)
-            names = arr(b.sample_names, int(no[-1]) if len(no) else 0, np.uint8).tobytes()
-            return {"flags": arr(b.flags, n * S, np.uint8).reshape(n, S),
-                    "ploidy": arr(b.ploidy, n * S, np.uint8).reshape(n, S),
-                    "allele": arr(b.allele, n * S * P, np.int16).reshape(n, S, P),
-                    "gq": arr(b.gq, n * S, np.int32).reshape(n, S),
-                    "dp": arr(b.dp, n * S, np.int32).reshape(n, S),
-                    "cell_off": arr(b.cell_off, n * S, np.int32).reshape(n, S),
-                    "part_offset": arr(b.part_offset, b.n_partitions + 1, np.int64),
-                    "samples": [names[no[i]:no[i + 1]] for i in range(S)],
+            return {"flags": _arr(b.flags, n * S, np.uint8).reshape(n, S),
+                    "ploidy": _arr(b.ploidy, n * S, np.uint8).reshape(n, S),
+                    "allele": _arr(b.allele, n * S * P, np.int16).reshape(n, S, P),
+                    "gq": _arr(b.gq, n * S, np.int32).reshape(n, S),
+                    "dp": _arr(b.dp, n * S, np.int32).reshape(n, S),
+                    "cell_off": _arr(b.cell_off, n * S, np.int32).reshape(n, S),
+                    "part_offset": _arr(b.part_offset, b.n_partitions + 1, np.int64),
+                    "samples": _name_list(b.sample_name_off, b.sample_names, S),
                     "n_samples": int(S), "max_ploidy": int(P), "n_gq_host": int(b.n_gq_host)}
         finally:
             lib().dq_genotype_batch_free(bp)
@@ -741,19 +735,14 @@ class Context:
         try:
             b = bp.contents
             n, K = b.n_variants, b.n_keys
-
-            def arr_of(ptr, k, dt):
-                if not k or not ptr:
-                    return np.zeros(0, dt)
-                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
-            g = {"flags": arr_of(b.flags, K * n, np.uint8).reshape(K, n),
-                 "n_values": arr_of(b.n_values, K * n, np.int32).reshape(K, n),
-                 "val_off": arr_of(b.val_off, K * n, np.int32).reshape(K, n),
-                 "val_len": arr_of(b.val_len, K * n, np.int32).reshape(K, n),
-                 "key_type": arr_of(b.key_type, K, np.int32), "key_width": arr_of(b.key_width, K, np.int32),
-                 "key_base": arr_of(b.key_base, K, np.int64),
-                 "ival": arr_of(b.ival, b.n_ival, np.int32), "fval": arr_of(b.fval, b.n_fval, np.float64),
-                 "part_offset": arr_of(b.part_offset, b.n_partitions + 1, np.int64),
+            g = {"flags": _arr(b.flags, K * n, np.uint8).reshape(K, n),
+                 "n_values": _arr(b.n_values, K * n, np.int32).reshape(K, n),
+                 "val_off": _arr(b.val_off, K * n, np.int32).reshape(K, n),
+                 "val_len": _arr(b.val_len, K * n, np.int32).reshape(K, n),
+                 "key_type": _arr(b.key_type, K, np.int32), "key_width": _arr(b.key_width, K, np.int32),
+                 "key_base": _arr(b.key_base, K, np.int64),
+                 "ival": _arr(b.ival, b.n_ival, np.int32), "fval": _arr(b.fval, b.n_fval, np.float64),
+                 "part_offset": _arr(b.part_offset, b.n_partitions + 1, np.int64),
                  "keys": ids, "n_float_host": int(b.n_float_host)}
             vals = []
             for q in range(K):
@@ -989,19 +978,14 @@ class Context:
         try:
             b = bp.contents
             n, K = b.n_records, b.n_keys
-
-            def arr_of(ptr, k, dt):
-                if not k or not ptr:
-                    return np.zeros(0, dt)
-                return np.ctypeslib.as_array(ptr, shape=(k,)).astype(dt, copy=True)
-            g = {"flags": arr_of(b.flags, K * n, np.uint8).reshape(K, n),
-                 "vtype": arr_of(b.vtype, K * n, np.uint8).reshape(K, n),
-                 "subtype": arr_of(b.subtype, K * n, np.uint8).reshape(K, n),
-                 "val_off": arr_of(b.val_off, K * n, np.int32).reshape(K, n),
-                 "val_len": arr_of(b.val_len, K * n, np.int32).reshape(K, n),
-                 "key_type": arr_of(b.key_type, K, np.int32), "key_base": arr_of(b.key_base, K, np.int64),
-                 "val": arr_of(b.val, b.n_val, np.uint32),
-                 "part_offset": arr_of(b.part_offset, b.n_partitions + 1, np.int64), "keys": ids}
+            g = {"flags": _arr(b.flags, K * n, np.uint8).reshape(K, n),
+                 "vtype": _arr(b.vtype, K * n, np.uint8).reshape(K, n),
+                 "subtype": _arr(b.subtype, K * n, np.uint8).reshape(K, n),
+                 "val_off": _arr(b.val_off, K * n, np.int32).reshape(K, n),
+                 "val_len": _arr(b.val_len, K * n, np.int32).reshape(K, n),
+                 "key_type": _arr(b.key_type, K, np.int32), "key_base": _arr(b.key_base, K, np.int64),
+                 "val": _arr(b.val, b.n_val, np.uint32),
+                 "part_offset": _arr(b.part_offset, b.n_partitions + 1, np.int64), "keys": ids}
             vals = []
             for q in range(K):
                 ty, at = int(g["key_type"][q]), int(g["key_base"][q])

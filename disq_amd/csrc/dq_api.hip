@@ -121,11 +121,15 @@ struct Bai {
 
 }  // namespace
 
+// dq_ctx::ev past the pipeline's own ev[0..7]: each name is the event recorded before a pass, the
+// one after it is the end of the pass.
+enum { EV_VCF_VALIDATE = 8, EV_VCF_DECODE = 10, EV_GT_CHECK = 12, EV_GT_DECODE = 14, EV_INFO_CHECK = 16,
+       EV_INFO_DECODE = 18, EV_TAG_CHECK = 20, EV_TAG_DECODE = 22, EV_COUNT = 24 };
+
 struct dq_ctx {
   dq_opts o{};
   hipStream_t s = nullptr;
-  hipEvent_t ev[24] = {};  // 8..11: the VCF validate and decode passes; 12..15: the genotype passes;
-                           // 16..19: the INFO passes; 20..23: the tag passes
+  hipEvent_t ev[EV_COUNT] = {};
   // DQ_EXPORT_STREAMS=2: the export's device-to-pinned copies alternate between s and this second
   // stream (a second DMA engine); created on first use
   hipStream_t sx = nullptr;
@@ -649,6 +653,228 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
   float ms = 0;
   (void)hipEventElapsedTime(&ms, a, b);
   return ms;
+}
+// the device time of the pass between ev[begin] and ev[begin + 1] (the EV_* pairs)
+double pass_ms(const dq_ctx* ctx, int begin) { return (double)ev_ms(ctx->ev[begin], ctx->ev[begin + 1]); }
+
+// One event of an index writer's timed interval, destroyed with its scope.
+struct Ev {
+  hipEvent_t e = nullptr;
+  ~Ev() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// ---- the binning index both index writers build (BinningIndexBuilder: DESIGN.md §bai, "Building
+// the .tbi").  build_bin_index queues the device passes and the downloads on ctx->s; the caller
+// synchronises the stream (inside its timed interval) before it reads the host vectors, so the
+// device buffers live here, past the call.
+struct BinIndex {
+  DevBuf d_woff, d_lin, d_in, d_sc, d_perm, d_chunks, d_bins;
+  int64_t nchunk = 0, nbin = 0;
+  std::vector<uint64_t> chunks;  // (begin, end) per chunk, the chunks of one bin together
+  std::vector<uint64_t> bins;    // (sequence << 16 | bin, first chunk) per bin, in device order
+  std::vector<uint64_t> lin;     // the sequences' 16 kbp windows at woff; ~0: no row touched it
+};
+
+// The rows' key / end / pos / start pointer (and end pointer: the tbi's, nullptr for the bai's
+// rows, which end where the next one starts) arrays on the device; np of the n rows have a
+// position (they come first); woff[r] is the first window of sequence r.  who and noun word the
+// one error of its own.
+int build_bin_index(dq_ctx* ctx, const uint64_t* key, const int32_t* end, const int32_t* pos,
+                    const uint64_t* voff, const uint64_t* vend, int64_t n, int64_t np, uint64_t fin,
+                    const std::vector<int64_t>& woff, const char* who, const char* noun, BinIndex* B) {
+  hipStream_t s = ctx->s;
+  const int64_t nwin = woff.back();
+  int rc;
+  B->lin.assign((size_t)nwin, 0);
+  if (np <= 0) return 0;
+  // linear index
+  HIPCHK(B->d_woff.ensure(8 * woff.size()));
+  HIPCHK(B->d_lin.ensure(8 * (size_t)std::max<int64_t>(1, nwin)));
+  HIPCHK(hipMemcpyAsync(B->d_woff.p, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(B->d_lin.p, 0xff, 8 * (size_t)nwin, s));
+  launch_bai_linear(key, end, pos, voff, n, B->d_woff.as<int64_t>(), nwin, B->d_lin.as<unsigned long long>(), s);
+  // the rows of one bin level are a sorted subsequence: stable partition by level
+  if ((rc = ensure_scan(ctx, n))) return rc;
+  HIPCHK(B->d_in.ensure(8 * (size_t)n));
+  HIPCHK(B->d_sc.ensure(8 * ((size_t)n + 1)));
+  HIPCHK(B->d_perm.ensure(8 * (size_t)np));
+  int64_t* in = B->d_in.as<int64_t>();
+  int64_t* sc = B->d_sc.as<int64_t>();
+  int64_t* perm = B->d_perm.as<int64_t>();
+  int64_t base = 0, tot = 0;
+  for (int la = 0; la < 6; la += 2) {
+    launch_bai_level_flags(key, n, la, in, s);
+    launch_exclusive_scan_i64(in, sc, n, ctx->tmp.as<int64_t>(), s);
+    if ((rc = get_i64(ctx, sc + n, &tot))) return rc;
+    const int64_t a = tot & 0xffffffff, b = tot >> 32;
+    launch_bai_level_scatter(key, n, la, sc, base, base + a, np, perm, s);
+    base += a + b;
+  }
+  if (base != np) RET(DQ_EDEVICE, std::string(who) + ": level partition lost " + noun);
+  // bin and chunk heads, their scan, the emit pass
+  launch_bai_heads(key, voff, n, fin, perm, np, in, s, vend);
+  launch_exclusive_scan_i64(in, sc, np, ctx->tmp.as<int64_t>(), s);
+  if ((rc = get_i64(ctx, sc + np, &tot))) return rc;
+  B->nchunk = tot & 0xffffffff;
+  B->nbin = tot >> 32;
+  HIPCHK(B->d_chunks.ensure(16 * (size_t)B->nchunk));
+  HIPCHK(B->d_bins.ensure(16 * (size_t)B->nbin));
+  launch_bai_emit(key, voff, n, fin, perm, np, in, sc, B->nchunk, B->nbin, B->d_chunks.as<uint64_t>(),
+                  B->d_bins.as<uint64_t>(), s, vend);
+  B->chunks.resize(2 * (size_t)B->nchunk);
+  B->bins.resize(2 * (size_t)B->nbin);
+  HIPCHK(hipMemcpyAsync(B->chunks.data(), B->d_chunks.p, 8 * B->chunks.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(B->bins.data(), B->d_bins.p, 8 * B->bins.size(), hipMemcpyDeviceToHost, s));
+  if (nwin) HIPCHK(hipMemcpyAsync(B->lin.data(), B->d_lin.p, 8 * B->lin.size(), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
+// little-endian appends (the host is little-endian, as every reader of these arrays here assumes)
+void p32(std::vector<uint8_t>& o, uint32_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 4); }
+void p64(std::vector<uint8_t>& o, uint64_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 8); }
+
+// A .bai's pseudo-bin 37450 of one reference: its span, then its mapped and unmapped counts.
+struct PseudoBin {
+  bool any;  // the reference has records: only then is the bin written
+  uint64_t w[4];
+};
+
+// The per-sequence part of a .bai and a .tbi (SAMv1 section 5.2): for each of the woff.size() - 1
+// sequences its bins in ascending order, each with its chunks, the pseudo-bin where the caller has
+// them (pseudo: one per sequence, or nullptr), then the linear index.
+void put_bin_index(std::vector<uint8_t>& o, const BinIndex& B, const std::vector<int64_t>& woff,
+                   const PseudoBin* pseudo) {
+  // bin headers into ascending (sequence, bin); a bin's chunk count runs to the next head in device order
+  std::vector<int64_t> order((size_t)B.nbin);
+  for (int64_t b = 0; b < B.nbin; b++) order[(size_t)b] = b;
+  std::sort(order.begin(), order.end(),
+            [&](int64_t x, int64_t y) { return B.bins[2 * (size_t)x] < B.bins[2 * (size_t)y]; });
+  size_t bi = 0;
+  for (int64_t r = 0; r + 1 < (int64_t)woff.size(); r++) {
+    size_t bj = bi;
+    while (bj < order.size() && (int64_t)(B.bins[2 * (size_t)order[bj]] >> 16) == r) bj++;
+    const bool any = pseudo && pseudo[r].any;
+    p32(o, (uint32_t)(bj - bi) + (any ? 1 : 0));
+    for (; bi < bj; bi++) {
+      const int64_t b = order[bi];
+      const int64_t c0 = (int64_t)B.bins[2 * (size_t)b + 1];
+      const int64_t c1 = b + 1 < B.nbin ? (int64_t)B.bins[2 * (size_t)b + 3] : B.nchunk;
+      p32(o, (uint32_t)(B.bins[2 * (size_t)b] & 0xffff));
+      p32(o, (uint32_t)(c1 - c0));
+      for (int64_t c = 2 * c0; c < 2 * c1; c++) p64(o, B.chunks[(size_t)c]);
+    }
+    if (any) {
+      p32(o, 37450);
+      p32(o, 2);
+      for (uint64_t v : pseudo[r].w) p64(o, v);
+    }
+    // linear index: an untouched window takes the previous window's offset (leading ones stay 0)
+    const int64_t ni = woff[(size_t)r + 1] - woff[(size_t)r];
+    p32(o, (uint32_t)ni);
+    uint64_t prev = 0;
+    for (int64_t w = 0; w < ni; w++) {
+      const uint64_t v = B.lin[(size_t)(woff[(size_t)r] + w)];
+      if (v != ~0ull) prev = v;
+      p64(o, prev);
+    }
+  }
+}
+
+// ---- batch exports (dq_text_read, dq_vcf_read, dq_vcf_genotypes, dq_vcf_info, dq_tags): each
+// callocs its struct, takes its arrays from one HostArrays, downloads them with one download_all and
+// frees the batch (dq_*_batch_free) when either reports a failure.
+
+// The host arrays of one batch, each of max(1, count) elements so that none is a null pointer.
+struct HostArrays {
+  bool failed = false;  // an allocation failed: the caller frees the batch and returns DQ_ENOMEM
+  template <typename T>
+  void one(T*& p, size_t count, bool zeroed = false) {
+    const size_t bytes = std::max<size_t>(1, count * sizeof(T));
+    p = (T*)(zeroed ? calloc(bytes, 1) : malloc(bytes));
+    if (!p) failed = true;
+  }
+  template <typename... T>
+  void get(size_t count, T*&... p) {  // several arrays of one length
+    (one(p, count), ...);
+  }
+};
+
+struct D2H {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+
+// Queues the non-empty copies on ctx->s and synchronises once.  The batch stays the caller's to free.
+int download_all(dq_ctx* ctx, std::initializer_list<D2H> copies, const char* who) {
+  bool ok = true;
+  for (const D2H& c : copies)
+    if (c.bytes) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->s) == hipSuccess;
+  if (hipStreamSynchronize(ctx->s) != hipSuccess || !ok)
+    RET(DQ_EDEVICE, std::string(who) + ": device to host copy failed");
+  return 0;
+}
+
+// part_offset (and part_digest, unless nullptr) of a text context's batch of n rows: one partition
+// per split of the text run.
+void fill_part_offsets(const dq_ctx* ctx, int64_t n, int64_t* off, uint64_t* digest) {
+  const size_t nsplit = ctx->tplans_h.size();
+  for (size_t i = 0; i < nsplit; i++) {
+    off[i] = ctx->parts_h[i].begin;
+    if (digest) digest[i] = ctx->parts_h[i].digest;
+  }
+  off[nsplit] = n;
+}
+
+// names, back to back in bytes; name r is bytes [off[r], off[r + 1])
+void pack_names(const std::vector<std::string>& names, int32_t* off, uint8_t* bytes) {
+  off[0] = 0;
+  for (size_t r = 0; r < names.size(); r++) {
+    memcpy(bytes + off[r], names[r].data(), names[r].size());
+    off[r + 1] = off[r] + (int32_t)names[r].size();
+  }
+}
+size_t names_bytes(const std::vector<std::string>& names) {
+  size_t n = 0;
+  for (const std::string& c : names) n += c.size();
+  return n;
+}
+
+// The kept lines of the text run as dq_text_read and dq_vcf_read export them: start, length and
+// hash per line, and -- where scan is set and there are lines -- off, the exclusive scan of a length
+// column (lens, or the lines' own lengths for nullptr), whose total is *nbytes.  The gather into data
+// is the caller's.
+struct TextLines {
+  DevBuf start, len, hash, off, data, tmp;
+};
+int text_line_export(dq_ctx* ctx, TextLines& L, const int32_t* lens, bool scan, int64_t* nbytes) {
+  hipStream_t s = ctx->s;
+  const int64_t n = ctx->t_nkept;
+  const size_t n1 = (size_t)std::max<int64_t>(1, n);
+  HIPCHK(L.start.ensure(8 * n1));
+  HIPCHK(L.len.ensure(4 * n1));
+  HIPCHK(L.hash.ensure(8 * n1));
+  HIPCHK(L.off.ensure(8 * (n1 + 1)));
+  HIPCHK(L.tmp.ensure(sizeof(int64_t) * (size_t)(4 * ((int64_t)n1 / 1024 + 1) + 4096)));
+  launch_text_export(ctx->t_kept.as<int64_t>(), n, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(),
+                     ctx->t_hash.as<uint64_t>(), L.start.as<int64_t>(), L.len.as<int32_t>(),
+                     L.hash.as<uint64_t>(), s);
+  *nbytes = 0;
+  if (!scan || n <= 0) return 0;
+  launch_exclusive_scan_i32(lens ? lens : L.len.as<int32_t>(), L.off.as<int64_t>(), n, L.tmp.as<int64_t>(), s);
+  return get_i64(ctx, L.off.as<int64_t>() + n, nbytes);
+}
+
+// The stats of a run that decodes behind the text run: the text run's values, hashes and digests
+// move into ms_plan, ms_records becomes the decode passes' device time.
+void text_stage_stats(const dq_ctx* ctx, double extra_ms, dq_stats* stats) {
+  if (!stats) return;
+  *stats = ctx->stats;
+  stats->ms_plan += stats->ms_records;
+  stats->ms_records = extra_ms;
+  stats->ms_total += extra_ms;
 }
 
 }  // namespace
@@ -3211,9 +3437,26 @@ int dq_set_splitting_index(dq_ctx* ctx, const uint8_t* sbi, int64_t len, int32_t
   return 0;
 }
 
+// The file pointer after decompressed byte E - 1, normalised as
+// BlockCompressedInputStream.getFilePointer does: inside a block it is (block, offset); a consumed
+// block points to the start of the next block (an empty one, the EOF block, included), the last
+// block and E == 0 to the file's end.
+static int final_pointer_at(dq_ctx* ctx, int64_t E, uint64_t* out) {
+  uint64_t fin = (uint64_t)ctx->flen << 16;
+  if (E > 0) {
+    std::vector<int64_t> uo((size_t)ctx->nblk + 1), bp((size_t)ctx->nblk);
+    HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
+    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end() - 1, E - 1) - uo.begin()) - 1;
+    if (j >= 0 && E < uo[(size_t)j + 1]) fin = ((uint64_t)bp[(size_t)j] << 16) | (uint64_t)(E - uo[(size_t)j]);
+    else if (j + 1 < ctx->nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
+  }
+  *out = fin;
+  return 0;
+}
+
 // finish(finalVirtualOffset): the file pointer after the last record (or after the header) of an
-// indexer-mode run, normalised as BlockCompressedInputStream.getFilePointer does: a consumed block
-// points to the next block's start (the EOF block, or the file end)
+// indexer-mode run
 static int final_pointer(dq_ctx* ctx, uint64_t* out) {
   const int64_t nrec = ctx->nrec;
   int64_t E = ctx->header_bytes;
@@ -3224,17 +3467,18 @@ static int final_pointer(dq_ctx* ctx, uint64_t* out) {
     HIPCHK(hipMemcpy(&bs, ctx->f_bs.as<int32_t>() + nrec - 1, 4, hipMemcpyDeviceToHost));
     E = lin + 4 + (int64_t)bs;
   }
-  std::vector<int64_t> uo((size_t)ctx->nblk + 1), bp((size_t)ctx->nblk);
-  HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
-  uint64_t fin = (uint64_t)ctx->flen << 16;
-  if (E > 0) {
-    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end() - 1, E - 1) - uo.begin()) - 1;
-    if (j >= 0 && E < uo[(size_t)j + 1]) fin = ((uint64_t)bp[(size_t)j] << 16) | (uint64_t)(E - uo[(size_t)j]);
-    else if (j + 1 < ctx->nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
-  }
-  *out = fin;
-  return 0;
+  return final_pointer_at(ctx, E, out);
+}
+
+// The indexer-mode run of dq_write_sbi, dq_write_bai and dq_sam_write_resident: every record once,
+// in file order, chained from the first record, no partition plans.
+static int run_index_only(dq_ctx* ctx) {
+  ctx->have_pipeline = false;
+  ctx->index_only = true;
+  const int rc = run_pipeline(ctx);
+  ctx->index_only = false;
+  ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
+  return rc;
 }
 
 int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_len) {
@@ -3242,11 +3486,7 @@ int dq_write_sbi(dq_ctx* ctx, int64_t granularity, uint8_t** out, int64_t* out_l
   ON_DEVICE(ctx);
   if (granularity <= 0) granularity = 4096;  // SBIIndexWriter.DEFAULT_GRANULARITY
   if (ctx->shard) RET(DQ_EINVAL, "dq_write_sbi indexes a whole file, not a shard");
-  ctx->have_pipeline = false;
-  ctx->index_only = true;
-  int rc = run_pipeline(ctx);
-  ctx->index_only = false;
-  ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
+  int rc = run_index_only(ctx);
   if (rc) return rc;
   const int64_t nrec = ctx->nrec, nent = (nrec + granularity - 1) / granularity;
   std::vector<uint64_t> ent((size_t)nent + 1);
@@ -3283,11 +3523,7 @@ int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
   if (!ctx || !out || !out_len) return DQ_EINVAL;
   ON_DEVICE(ctx);
   if (ctx->shard) RET(DQ_EINVAL, "dq_write_bai indexes a whole file, not a shard");
-  ctx->have_pipeline = false;
-  ctx->index_only = true;
-  int rc = run_pipeline(ctx);
-  ctx->index_only = false;
-  ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
+  int rc = run_index_only(ctx);
   if (rc) return rc;
   if (ms) *ms = 0;
   const int64_t n = ctx->nrec;
@@ -3296,19 +3532,15 @@ int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
   if (n > INT32_MAX) RET(DQ_EINVAL, "dq_write_bai: more than 2147483647 records");
   uint64_t fin = 0;
   if ((rc = final_pointer(ctx, &fin))) return rc;
-  struct Ev {
-    hipEvent_t e = nullptr;
-    ~Ev() {
-      if (e) (void)hipEventDestroy(e);
-    }
-  } e0, e1;
+  Ev e0, e1;
   HIPCHK(hipEventCreate(&e0.e));
   HIPCHK(hipEventCreate(&e1.e));
   HIPCHK(hipEventRecord(e0.e, s));
   // hd: status, n_no_coor, then 5 words per reference (launch_bai_keys)
   std::vector<unsigned long long> hd(2 + 5 * (size_t)n_ref, 0);
   hd[0] = ~0ull;
-  DevBuf d_hd, d_key, d_end, d_span, d_woff, d_lin, d_in, d_sc, d_perm, d_chunks, d_bins;
+  DevBuf d_hd, d_key, d_end, d_span;
+  BinIndex B;
   const uint64_t* voff = ctx->f_voff.as<uint64_t>();
   if (n) {
     HIPCHK(d_hd.ensure(8 * hd.size()));
@@ -3332,104 +3564,29 @@ int dq_write_bai(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) {
   const int64_t no_coor = (int64_t)hd[1], np = n - no_coor;
   std::vector<int64_t> woff((size_t)n_ref + 1, 0);
   for (int32_t r = 0; r < n_ref; r++) woff[(size_t)r + 1] = woff[(size_t)r] + (int64_t)hd[2 + 5 * (size_t)r + 4];
-  const int64_t nwin = woff[(size_t)n_ref];
-  int64_t nchunk = 0, nbin = 0;
-  std::vector<uint64_t> lin((size_t)nwin), chunks, bins, span(2 * (size_t)n_ref, 0);
+  std::vector<uint64_t> span(2 * (size_t)n_ref, 0);
   if (np > 0) {
     HIPCHK(d_span.ensure(8 * span.size()));
     launch_bai_refspan(d_hd.as<unsigned long long>() + 2, n_ref, voff, n, fin, d_span.as<uint64_t>(), s);
-    // linear index
-    HIPCHK(d_woff.ensure(8 * woff.size()));
-    HIPCHK(d_lin.ensure(8 * (size_t)nwin));
-    HIPCHK(hipMemcpyAsync(d_woff.p, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_lin.p, 0xff, 8 * (size_t)nwin, s));
-    launch_bai_linear(d_key.as<uint64_t>(), d_end.as<int32_t>(), ctx->f_pos.as<int32_t>(), voff, n,
-                      d_woff.as<int64_t>(), nwin, d_lin.as<unsigned long long>(), s);
-    // the records of one bin level are a sorted subsequence: stable partition by level
-    if ((rc = ensure_scan(ctx, n))) return rc;
-    HIPCHK(d_in.ensure(8 * (size_t)n));
-    HIPCHK(d_sc.ensure(8 * ((size_t)n + 1)));
-    HIPCHK(d_perm.ensure(8 * (size_t)np));
-    int64_t base = 0;
-    for (int la = 0; la < 6; la += 2) {
-      launch_bai_level_flags(d_key.as<uint64_t>(), n, la, d_in.as<int64_t>(), s);
-      launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
-      int64_t tot = 0;
-      if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
-      const int64_t a = tot & 0xffffffff, b = tot >> 32;
-      launch_bai_level_scatter(d_key.as<uint64_t>(), n, la, d_sc.as<int64_t>(), base, base + a, np,
-                               d_perm.as<int64_t>(), s);
-      base += a + b;
-    }
-    if (base != np) RET(DQ_EDEVICE, "dq_write_bai: level partition lost records");
-    // bin and chunk heads, their scan, the emit pass
-    launch_bai_heads(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), np, d_in.as<int64_t>(), s);
-    launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), np, ctx->tmp.as<int64_t>(), s);
-    int64_t tot = 0;
-    if ((rc = get_i64(ctx, d_sc.as<int64_t>() + np, &tot))) return rc;
-    nchunk = tot & 0xffffffff;
-    nbin = tot >> 32;
-    HIPCHK(d_chunks.ensure(16 * (size_t)nchunk));
-    HIPCHK(d_bins.ensure(16 * (size_t)nbin));
-    launch_bai_emit(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), np, d_in.as<int64_t>(),
-                    d_sc.as<int64_t>(), nchunk, nbin, d_chunks.as<uint64_t>(), d_bins.as<uint64_t>(), s);
-    chunks.resize(2 * (size_t)nchunk);
-    bins.resize(2 * (size_t)nbin);
-    HIPCHK(hipMemcpyAsync(chunks.data(), d_chunks.p, 8 * chunks.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(bins.data(), d_bins.p, 8 * bins.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(span.data(), d_span.p, 8 * span.size(), hipMemcpyDeviceToHost, s));
-    if (nwin) HIPCHK(hipMemcpyAsync(lin.data(), d_lin.p, 8 * lin.size(), hipMemcpyDeviceToHost, s));
   }
+  if ((rc = build_bin_index(ctx, d_key.as<uint64_t>(), d_end.as<int32_t>(), ctx->f_pos.as<int32_t>(), voff,
+                            nullptr, n, np, fin, woff, "dq_write_bai", "records", &B)))
+    return rc;
+  if (np > 0) HIPCHK(hipMemcpyAsync(span.data(), d_span.p, 8 * span.size(), hipMemcpyDeviceToHost, s));
   HIPCHK(hipEventRecord(e1.e, s));
   HIPCHK(hipStreamSynchronize(s));
   if (ms) *ms = ev_ms(e0.e, e1.e);
-  // bin headers into ascending (ref, bin); a bin's chunk count runs to the next head in device order
-  std::vector<int64_t> order((size_t)nbin);
-  for (int64_t b = 0; b < nbin; b++) order[(size_t)b] = b;
-  std::sort(order.begin(), order.end(),
-            [&](int64_t x, int64_t y) { return bins[2 * (size_t)x] < bins[2 * (size_t)y]; });
-  std::vector<uint8_t> o;
-  auto p32 = [&](uint32_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
-  auto p64 = [&](uint64_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 8); };
-  o.insert(o.end(), {'B', 'A', 'I', 1});
-  p32((uint32_t)n_ref);
-  size_t bi = 0;
+  // pseudo-bin 37450 of a reference with records: its span, its mapped / unmapped counts
+  std::vector<PseudoBin> pseudo((size_t)n_ref);
   for (int32_t r = 0; r < n_ref; r++) {
     const unsigned long long* m = hd.data() + 2 + 5 * (size_t)r;
-    size_t bj = bi;
-    while (bj < order.size() && (int64_t)(bins[2 * (size_t)order[bj]] >> 16) == r) bj++;
-    const bool any = m[1] != 0;
-    p32((uint32_t)(bj - bi) + (any ? 1 : 0));
-    for (; bi < bj; bi++) {
-      const int64_t b = order[bi];
-      const int64_t c0 = (int64_t)bins[2 * (size_t)b + 1];
-      const int64_t c1 = b + 1 < nbin ? (int64_t)bins[2 * (size_t)b + 3] : nchunk;
-      p32((uint32_t)(bins[2 * (size_t)b] & 0xffff));
-      p32((uint32_t)(c1 - c0));
-      for (int64_t c = c0; c < c1; c++) {
-        p64(chunks[2 * (size_t)c]);
-        p64(chunks[2 * (size_t)c + 1]);
-      }
-    }
-    if (any) {  // pseudo-bin 37450: the reference's span, its mapped / unmapped counts
-      p32(37450);
-      p32(2);
-      p64(span[2 * (size_t)r]);
-      p64(span[2 * (size_t)r + 1]);
-      p64(m[2]);
-      p64(m[3]);
-    }
-    // linear index: an untouched window takes the previous window's offset (leading ones stay 0)
-    const int64_t ni = woff[(size_t)r + 1] - woff[(size_t)r];
-    p32((uint32_t)ni);
-    uint64_t prev = 0;
-    for (int64_t w = 0; w < ni; w++) {
-      const uint64_t v = lin[(size_t)(woff[(size_t)r] + w)];
-      if (v != ~0ull) prev = v;
-      p64(prev);
-    }
+    pseudo[(size_t)r] = PseudoBin{m[1] != 0, {span[2 * (size_t)r], span[2 * (size_t)r + 1], m[2], m[3]}};
   }
-  p64((uint64_t)no_coor);
+  std::vector<uint8_t> o;
+  o.insert(o.end(), {'B', 'A', 'I', 1});
+  p32(o, (uint32_t)n_ref);
+  put_bin_index(o, B, woff, pseudo.data());
+  p64(o, (uint64_t)no_coor);
   uint8_t* b = (uint8_t*)malloc(o.size());
   if (!b) return DQ_ENOMEM;
   memcpy(b, o.data(), o.size());
@@ -3945,12 +4102,7 @@ int dq_sam_write_resident(dq_ctx* ctx, int64_t* out_len, double* ms) {
     if ((rc = get_i64(ctx, ctx->rec_lin.as<int64_t>() + ctx->nrec, &raw_len))) return rc;
     if (ctx->nrec == 0) raw_len = 0;
   } else {  // every record once, in file order: the index-only run dq_write_bai makes
-    ctx->have_pipeline = false;
-    ctx->index_only = true;
-    rc = run_pipeline(ctx);
-    ctx->index_only = false;
-    ctx->have_pipeline = false;  // the next call re-plans with the caller's settings
-    if (rc) return rc;
+    if ((rc = run_index_only(ctx))) return rc;
     raw_len = ctx->ulen;
   }
   if ((rc = samw_run(ctx, ctx->ref_name, ctx->rec_src(), raw_len, ctx->rec_lin.as<int64_t>(), ctx->nrec, ms)))
@@ -3987,54 +4139,37 @@ int dq_text_read(dq_ctx* ctx, int32_t drop_header_lines, dq_text_batch** out) {
   if (rc) return rc;
   hipStream_t s = ctx->s;
   const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
-  const size_t n1 = (size_t)std::max<int64_t>(1, n);
-  DevBuf o_start, o_len, o_hash, o_off, o_data, tmp;
-  HIPCHK(o_start.ensure(8 * n1));
-  HIPCHK(o_len.ensure(4 * n1));
-  HIPCHK(o_hash.ensure(8 * n1));
-  HIPCHK(o_off.ensure(8 * (n1 + 1)));
-  HIPCHK(tmp.ensure(sizeof(int64_t) * (size_t)(4 * ((int64_t)n1 / 1024 + 1) + 4096)));
-  launch_text_export(ctx->t_kept.as<int64_t>(), n, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(),
-                     ctx->t_hash.as<uint64_t>(), o_start.as<int64_t>(), o_len.as<int32_t>(),
-                     o_hash.as<uint64_t>(), s);
-  if (n > 0) launch_exclusive_scan_i32(o_len.as<int32_t>(), o_off.as<int64_t>(), n, tmp.as<int64_t>(), s);
+  const size_t nn = (size_t)n;
+  TextLines L;
   int64_t nbytes = 0;
-  if (n > 0 && (rc = get_i64(ctx, o_off.as<int64_t>() + n, &nbytes))) return rc;
-  HIPCHK(o_data.ensure((size_t)std::max<int64_t>(1, nbytes)));
+  if ((rc = text_line_export(ctx, L, nullptr, true, &nbytes))) return rc;
+  HIPCHK(L.data.ensure((size_t)std::max<int64_t>(1, nbytes)));
   launch_text_gather(ctx->U.as<uint8_t>(), ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(),
-                     ctx->t_kept.as<int64_t>(), o_off.as<int64_t>(), n, o_data.as<uint8_t>(), s);
+                     ctx->t_kept.as<int64_t>(), L.off.as<int64_t>(), n, L.data.as<uint8_t>(), s);
   dq_text_batch* b = (dq_text_batch*)calloc(1, sizeof(dq_text_batch));
   if (!b) return DQ_ENOMEM;
   b->n_lines = n;
   b->n_partitions = nsplit;
-  b->line_offset = (int64_t*)malloc(8 * n1);
-  b->line_len = (int32_t*)malloc(4 * n1);
-  b->hash = (uint64_t*)malloc(8 * n1);
-  b->data_offset = (int64_t*)malloc(8 * (n1 + 1));
-  b->data = (uint8_t*)malloc((size_t)std::max<int64_t>(1, nbytes));
-  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
-  b->part_digest = (uint64_t*)malloc(8 * (size_t)std::max<int64_t>(1, nsplit));
-  if (!b->line_offset || !b->line_len || !b->hash || !b->data_offset || !b->data || !b->part_offset ||
-      !b->part_digest) {
+  b->n_bytes = nbytes;
+  HostArrays ha;
+  ha.get(nn, b->line_offset, b->line_len, b->hash);
+  ha.one(b->data_offset, nn + 1, n == 0);  // no line, no copy: data_offset[0] = 0
+  ha.get((size_t)nbytes, b->data);
+  ha.get((size_t)nsplit + 1, b->part_offset);
+  ha.get((size_t)nsplit, b->part_digest);
+  if (ha.failed) {
     dq_text_batch_free(b);
     return DQ_ENOMEM;
   }
-  if (n > 0) {
-    HIPCHK(hipMemcpyAsync(b->line_offset, o_start.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(b->line_len, o_len.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(b->hash, o_hash.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(b->data_offset, o_off.p, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
-  } else {
-    b->data_offset[0] = 0;
+  if ((rc = download_all(ctx,
+                         {{b->line_offset, L.start.p, 8 * nn}, {b->line_len, L.len.p, 4 * nn},
+                          {b->hash, L.hash.p, 8 * nn}, {b->data_offset, L.off.p, n > 0 ? 8 * (nn + 1) : 0},
+                          {b->data, L.data.p, (size_t)nbytes}},
+                         "dq_text_read"))) {
+    dq_text_batch_free(b);
+    return rc;
   }
-  if (nbytes > 0) HIPCHK(hipMemcpyAsync(b->data, o_data.p, (size_t)nbytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  b->n_bytes = nbytes;
-  for (int64_t i = 0; i < nsplit; i++) {
-    b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
-    b->part_digest[i] = ctx->parts_h[(size_t)i].digest;
-  }
-  b->part_offset[nsplit] = n;
+  fill_part_offsets(ctx, n, b->part_offset, b->part_digest);
   *out = b;
   return 0;
 }
@@ -4100,10 +4235,10 @@ static int vcf_run(dq_ctx* ctx) {
   unsigned long long sc[2] = {~0ull, 0};
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipMemcpy(d_scal, init, sizeof init, hipMemcpyHostToDevice));
-  HIPCHK(hipEventRecord(ctx->ev[8], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_VCF_VALIDATE], s));
   launch_vcf_validate(U, ulen, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(), ctx->t_idx.as<int64_t>(),
                       total, ctx->vcf_G, ctx->vcf_ctg, d_scal, s);
-  HIPCHK(hipEventRecord(ctx->ev[9], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_VCF_VALIDATE + 1], s));
   HIPCHK(hipMemcpyAsync(sc, d_scal, 16, hipMemcpyDeviceToHost, s));  // one download: both words
   HIPCHK(hipStreamSynchronize(s));
   if (sc[0] != ~0ull) {
@@ -4121,11 +4256,11 @@ static int vcf_run(dq_ctx* ctx) {
         (rc = ensure_all(ctx, ctx->v_fix, 24 * (size_t)std::max<int64_t>(1, nund))))
       return rc;
   }
-  HIPCHK(hipEventRecord(ctx->ev[10], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_VCF_DECODE], s));
   launch_vcf_decode(U, ulen, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(), total,
                     ctx->t_kept.as<int64_t>(), n, ctx->vcf_G, ctx->vcf_ctg, vcf_cols(ctx),
                     ctx->v_fix.as<int64_t>(), nund, d_scal + 2, s);
-  HIPCHK(hipEventRecord(ctx->ev[11], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_VCF_DECODE + 1], s));
   // ---- QUAL fix-ups: the texts off the exact fast path, converted by strtod (normally none)
   int64_t cnt = 0;
   if ((rc = host_fixups(ctx, d_scal + 2, nund, true, ctx->v_fix.p, 3, U, ulen, "VCF decode pass",
@@ -4139,7 +4274,7 @@ static int vcf_run(dq_ctx* ctx) {
                         })))
     return rc;
   ctx->vcf_nqual_host = cnt;
-  ctx->vcf_ms = (double)ev_ms(ctx->ev[8], ctx->ev[9]) + (double)ev_ms(ctx->ev[10], ctx->ev[11]);
+  ctx->vcf_ms = pass_ms(ctx, EV_VCF_VALIDATE) + pass_ms(ctx, EV_VCF_DECODE);
   ctx->vcf_gen = ctx->text_gen;
   return 0;
 }
@@ -4153,12 +4288,7 @@ int dq_vcf_run(dq_ctx* ctx, dq_stats* stats) {
   ctx->have_text = false;
   int rc = vcf_run(ctx);
   if (rc) return rc;
-  if (stats) {
-    *stats = ctx->stats;
-    stats->ms_plan += stats->ms_records;  // the text run's values, hashes and digests
-    stats->ms_records = ctx->vcf_ms;      // validate + decode
-    stats->ms_total += ctx->vcf_ms;
-  }
+  text_stage_stats(ctx, ctx->vcf_ms, stats);  // validate + decode
   return 0;
 }
 
@@ -4172,93 +4302,56 @@ int dq_vcf_read(dq_ctx* ctx, int32_t mode, dq_variant_batch** out) {
   if (rc) return rc;
   hipStream_t s = ctx->s;
   const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
-  const size_t n1 = (size_t)std::max<int64_t>(1, n);
-  DevBuf o_start, o_len, o_hash, o_off, o_data, tmp;
-  HIPCHK(o_start.ensure(8 * n1));
-  HIPCHK(o_len.ensure(4 * n1));
-  HIPCHK(o_hash.ensure(8 * n1));
-  HIPCHK(o_off.ensure(8 * (n1 + 1)));
-  HIPCHK(tmp.ensure(sizeof(int64_t) * (size_t)(4 * ((int64_t)n1 / 1024 + 1) + 4096)));
-  launch_text_export(ctx->t_kept.as<int64_t>(), n, ctx->t_vs.as<int64_t>(), ctx->t_vl.as<int32_t>(),
-                     ctx->t_hash.as<uint64_t>(), o_start.as<int64_t>(), o_len.as<int32_t>(),
-                     o_hash.as<uint64_t>(), s);
+  const size_t nn = (size_t)n;
+  const bool with_data = mode != DQ_VCF_EXPORT_FIELDS;
+  TextLines L;
   int64_t nbytes = 0;
-  if (mode != DQ_VCF_EXPORT_FIELDS && n > 0) {
-    const int32_t* lens = mode == DQ_VCF_EXPORT_SITES ? ctx->v_sitelen.as<int32_t>() : o_len.as<int32_t>();
-    launch_exclusive_scan_i32(lens, o_off.as<int64_t>(), n, tmp.as<int64_t>(), s);
-    if ((rc = get_i64(ctx, o_off.as<int64_t>() + n, &nbytes))) return rc;
+  const int32_t* site_len = mode == DQ_VCF_EXPORT_SITES ? ctx->v_sitelen.as<int32_t>() : nullptr;
+  if ((rc = text_line_export(ctx, L, site_len, with_data, &nbytes))) return rc;
+  if (with_data && n > 0) {
     if (nbytes < 0) RET(DQ_EDEVICE, "dq_vcf_read: bad byte total");
-    HIPCHK(o_data.ensure((size_t)std::max<int64_t>(1, nbytes)));
-    launch_vcf_gather(ctx->U.as<uint8_t>(), ctx->ulen, o_start.as<int64_t>(), lens, o_off.as<int64_t>(), n,
-                      o_data.as<uint8_t>(), s);
+    HIPCHK(L.data.ensure((size_t)std::max<int64_t>(1, nbytes)));
+    launch_vcf_gather(ctx->U.as<uint8_t>(), ctx->ulen, L.start.as<int64_t>(), site_len ? site_len : L.len.as<int32_t>(),
+                      L.off.as<int64_t>(), n, L.data.as<uint8_t>(), s);
   }
   dq_variant_batch* b = (dq_variant_batch*)calloc(1, sizeof(dq_variant_batch));
   if (!b) return DQ_ENOMEM;
-  const bool with_data = mode != DQ_VCF_EXPORT_FIELDS;
   const size_t nc = ctx->vcf_contigs.size();
-  size_t name_bytes = 0;
-  for (const std::string& c : ctx->vcf_contigs) name_bytes += c.size();
   b->n_variants = n;
   b->n_partitions = nsplit;
-  b->line_offset = (int64_t*)malloc(8 * n1);
-  b->line_len = (int32_t*)malloc(4 * n1);
-  b->hash = (uint64_t*)malloc(8 * n1);
-  int32_t** c4[] = {&b->contig, &b->pos, &b->end, (int32_t**)&b->flags, &b->n_alt, &b->n_filter,
-                    &b->n_info, &b->n_sample_cols};
-  const DevBuf* d4[] = {&ctx->v_contig, &ctx->v_pos, &ctx->v_end, &ctx->v_flags, &ctx->v_nalt,
-                        &ctx->v_nfilter, &ctx->v_ninfo, &ctx->v_nsample};
-  bool ok = b->line_offset && b->line_len && b->hash;
-  for (auto** c : c4) ok = (*c = (int32_t*)malloc(4 * n1)) != nullptr && ok;
-  b->qual = (double*)malloc(8 * n1);
-  b->col_end = (int32_t*)malloc(32 * n1);
-  b->data_offset = (int64_t*)calloc(n1 + 1, 8);
-  b->data = with_data ? (uint8_t*)malloc((size_t)std::max<int64_t>(1, nbytes)) : nullptr;
-  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
-  b->part_digest = (uint64_t*)malloc(8 * (size_t)std::max<int64_t>(1, nsplit));
-  b->contig_name_off = (int32_t*)malloc(4 * (nc + 1));
-  b->contig_names = (uint8_t*)malloc(std::max<size_t>(1, name_bytes));
-  ok = ok && b->qual && b->col_end && b->data_offset && (b->data || !with_data) && b->part_offset &&
-       b->part_digest && b->contig_name_off && b->contig_names;
-  if (!ok) {
+  b->n_bytes = nbytes;
+  b->n_contigs = (int32_t)nc;
+  b->n_qual_host = ctx->vcf_nqual_host;
+  HostArrays ha;
+  ha.get(nn, b->line_offset, b->line_len, b->hash, b->contig, b->pos, b->end, b->flags, b->n_alt, b->n_filter,
+         b->n_info, b->n_sample_cols, b->qual);
+  ha.get(8 * nn, b->col_end);
+  ha.one(b->data_offset, std::max<size_t>(1, nn) + 1, true);  // stays zero without data
+  if (with_data) ha.get((size_t)nbytes, b->data);
+  ha.get((size_t)nsplit + 1, b->part_offset);
+  ha.get((size_t)nsplit, b->part_digest);
+  ha.get(nc + 1, b->contig_name_off);
+  ha.get(names_bytes(ctx->vcf_contigs), b->contig_names);
+  if (ha.failed) {
     dq_variant_batch_free(b);
     return DQ_ENOMEM;
   }
-#define VCF_D2H(dst, src, bytes)                                                       \
-  do {                                                                                 \
-    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {     \
-      dq_variant_batch_free(b);                                                        \
-      RET(DQ_EDEVICE, "dq_vcf_read: device to host copy failed");                      \
-    }                                                                                  \
-  } while (0)
-  if (n > 0) {
-    VCF_D2H(b->line_offset, o_start.p, 8 * (size_t)n);
-    VCF_D2H(b->line_len, o_len.p, 4 * (size_t)n);
-    VCF_D2H(b->hash, o_hash.p, 8 * (size_t)n);
-    for (size_t i = 0; i < 8; i++) VCF_D2H(*c4[i], d4[i]->p, 4 * (size_t)n);
-    VCF_D2H(b->qual, ctx->v_qual.p, 8 * (size_t)n);
-    VCF_D2H(b->col_end, ctx->v_colend.p, 32 * (size_t)n);
-    if (with_data) VCF_D2H(b->data_offset, o_off.p, 8 * (size_t)(n + 1));
-  }
-  if (nbytes > 0) VCF_D2H(b->data, o_data.p, (size_t)nbytes);
-#undef VCF_D2H
-  if (hipStreamSynchronize(s) != hipSuccess) {
+  if ((rc = download_all(ctx,
+                         {{b->line_offset, L.start.p, 8 * nn}, {b->line_len, L.len.p, 4 * nn},
+                          {b->hash, L.hash.p, 8 * nn}, {b->contig, ctx->v_contig.p, 4 * nn},
+                          {b->pos, ctx->v_pos.p, 4 * nn}, {b->end, ctx->v_end.p, 4 * nn},
+                          {b->flags, ctx->v_flags.p, 4 * nn}, {b->n_alt, ctx->v_nalt.p, 4 * nn},
+                          {b->n_filter, ctx->v_nfilter.p, 4 * nn}, {b->n_info, ctx->v_ninfo.p, 4 * nn},
+                          {b->n_sample_cols, ctx->v_nsample.p, 4 * nn}, {b->qual, ctx->v_qual.p, 8 * nn},
+                          {b->col_end, ctx->v_colend.p, 32 * nn},
+                          {b->data_offset, L.off.p, with_data && n > 0 ? 8 * (nn + 1) : 0},
+                          {b->data, L.data.p, (size_t)nbytes}},
+                         "dq_vcf_read"))) {
     dq_variant_batch_free(b);
-    RET(DQ_EDEVICE, "dq_vcf_read: device to host copy failed");
+    return rc;
   }
-  b->n_bytes = nbytes;
-  for (int64_t i = 0; i < nsplit; i++) {
-    b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
-    b->part_digest[i] = ctx->parts_h[(size_t)i].digest;
-  }
-  b->part_offset[nsplit] = n;
-  b->n_contigs = (int32_t)nc;
-  b->contig_name_off[0] = 0;
-  for (size_t r = 0; r < nc; r++) {
-    const std::string& c = ctx->vcf_contigs[r];
-    memcpy(b->contig_names + b->contig_name_off[r], c.data(), c.size());
-    b->contig_name_off[r + 1] = b->contig_name_off[r] + (int32_t)c.size();
-  }
-  b->n_qual_host = ctx->vcf_nqual_host;
+  fill_part_offsets(ctx, n, b->part_offset, b->part_digest);
+  pack_names(ctx->vcf_contigs, b->contig_name_off, b->contig_names);
   *out = b;
   return 0;
 }
@@ -4310,9 +4403,9 @@ static int gt_run(dq_ctx* ctx) {
     unsigned long long sc[3] = {~0ull, 0, 0};
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipMemcpy(d_scal, init, sizeof init, hipMemcpyHostToDevice));
-    HIPCHK(hipEventRecord(ctx->ev[12], s));
+    HIPCHK(hipEventRecord(ctx->ev[EV_GT_CHECK], s));
     dq::launch_gt_check(in, d_scal, s);
-    HIPCHK(hipEventRecord(ctx->ev[13], s));
+    HIPCHK(hipEventRecord(ctx->ev[EV_GT_CHECK + 1], s));
     HIPCHK(hipMemcpyAsync(sc, d_scal, sizeof sc, hipMemcpyDeviceToHost, s));  // one download: all three
     HIPCHK(hipStreamSynchronize(s));
     if (sc[0] != ~0ull) {
@@ -4335,9 +4428,9 @@ static int gt_run(dq_ctx* ctx) {
       return rc;
     const dq::GtCols out{ctx->g_flags.as<uint8_t>(), ctx->g_ploidy.as<uint8_t>(), ctx->g_allele.as<int16_t>(),
                          ctx->g_gq.as<int32_t>(),    ctx->g_dp.as<int32_t>(),     ctx->g_off.as<int32_t>()};
-    HIPCHK(hipEventRecord(ctx->ev[14], s));
+    HIPCHK(hipEventRecord(ctx->ev[EV_GT_DECODE], s));
     dq::launch_gt_decode(in, out, P, ctx->g_fix.as<int64_t>(), nhost, d_scal, s);
-    HIPCHK(hipEventRecord(ctx->ev[15], s));
+    HIPCHK(hipEventRecord(ctx->ev[EV_GT_DECODE + 1], s));
     // ---- GQ fix-ups: the texts off the digit path, strtod and Java's rounding (normally none)
     if ((rc = host_fixups(ctx, d_scal + 3, nhost, false, ctx->g_fix.p, 3, ctx->U.as<uint8_t>(), ctx->ulen,
                           "VCF genotype decode pass", "its GQ texts for the host differ from the check pass's count",
@@ -4351,7 +4444,7 @@ static int gt_run(dq_ctx* ctx) {
       return rc;
     ctx->gt_P = P;
     ctx->gt_nhost = nhost;
-    ctx->gt_ms = (double)ev_ms(ctx->ev[12], ctx->ev[13]) + (double)ev_ms(ctx->ev[14], ctx->ev[15]);
+    ctx->gt_ms = pass_ms(ctx, EV_GT_CHECK) + pass_ms(ctx, EV_GT_DECODE);
   }
   ctx->gt_gen = ctx->text_gen;
   return 0;
@@ -4362,12 +4455,7 @@ int dq_vcf_genotypes_run(dq_ctx* ctx, dq_stats* stats) {
   ON_DEVICE(ctx);
   int rc = gt_run(ctx);
   if (rc) return rc;
-  if (stats) {
-    *stats = ctx->stats;
-    stats->ms_plan += stats->ms_records;               // as dq_vcf_run
-    stats->ms_records = ctx->vcf_ms + ctx->gt_ms;      // validate + decode, genotype check + decode
-    stats->ms_total += ctx->vcf_ms + ctx->gt_ms;
-  }
+  text_stage_stats(ctx, ctx->vcf_ms + ctx->gt_ms, stats);  // validate + decode, genotype check + decode
   return 0;
 }
 
@@ -4377,53 +4465,36 @@ int dq_vcf_genotypes(dq_ctx* ctx, dq_genotype_batch** out) {
   *out = nullptr;
   int rc = gt_run(ctx);
   if (rc) return rc;
-  hipStream_t s = ctx->s;
   const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
   const size_t S = ctx->vcf_samples.size(), P = (size_t)ctx->gt_P;
-  const size_t cells = (size_t)n * S, c1 = std::max<size_t>(1, cells);
-  size_t name_bytes = 0;
-  for (const std::string& c : ctx->vcf_samples) name_bytes += c.size();
+  const size_t cells = (size_t)n * S;
   dq_genotype_batch* b = (dq_genotype_batch*)calloc(1, sizeof(dq_genotype_batch));
   if (!b) return DQ_ENOMEM;
   b->n_variants = n;
   b->n_samples = (int32_t)S;
   b->max_ploidy = (int32_t)P;
-  b->flags = (uint8_t*)malloc(c1);
-  b->ploidy = (uint8_t*)malloc(c1);
-  b->allele = (int16_t*)malloc(2 * std::max<size_t>(1, cells * P));
-  b->gq = (int32_t*)malloc(4 * c1);
-  b->dp = (int32_t*)malloc(4 * c1);
-  b->cell_off = (int32_t*)malloc(4 * c1);
-  b->sample_name_off = (int32_t*)malloc(4 * (S + 1));
-  b->sample_names = (uint8_t*)malloc(std::max<size_t>(1, name_bytes));
   b->n_partitions = nsplit;
-  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
-  if (!(b->flags && b->ploidy && b->allele && b->gq && b->dp && b->cell_off && b->sample_name_off &&
-        b->sample_names && b->part_offset)) {
+  b->n_gq_host = ctx->gt_nhost;
+  HostArrays ha;
+  ha.get(cells, b->flags, b->ploidy, b->gq, b->dp, b->cell_off);
+  ha.get(cells * P, b->allele);
+  ha.get(S + 1, b->sample_name_off);
+  ha.get(names_bytes(ctx->vcf_samples), b->sample_names);
+  ha.get((size_t)nsplit + 1, b->part_offset);
+  if (ha.failed) {
     dq_genotype_batch_free(b);
     return DQ_ENOMEM;
   }
-  if (cells > 0) {
-    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
-        {b->flags, ctx->g_flags.p, cells},         {b->ploidy, ctx->g_ploidy.p, cells},
-        {b->allele, ctx->g_allele.p, 2 * cells * P}, {b->gq, ctx->g_gq.p, 4 * cells},
-        {b->dp, ctx->g_dp.p, 4 * cells},           {b->cell_off, ctx->g_off.p, 4 * cells}};
-    bool ok = true;
-    for (const auto& c : cp) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
-      dq_genotype_batch_free(b);
-      RET(DQ_EDEVICE, "dq_vcf_genotypes: device to host copy failed");
-    }
+  if (cells > 0 && (rc = download_all(ctx,
+                                      {{b->flags, ctx->g_flags.p, cells}, {b->ploidy, ctx->g_ploidy.p, cells},
+                                       {b->allele, ctx->g_allele.p, 2 * cells * P}, {b->gq, ctx->g_gq.p, 4 * cells},
+                                       {b->dp, ctx->g_dp.p, 4 * cells}, {b->cell_off, ctx->g_off.p, 4 * cells}},
+                                      "dq_vcf_genotypes"))) {
+    dq_genotype_batch_free(b);
+    return rc;
   }
-  b->sample_name_off[0] = 0;
-  for (size_t r = 0; r < S; r++) {
-    const std::string& c = ctx->vcf_samples[r];
-    memcpy(b->sample_names + b->sample_name_off[r], c.data(), c.size());
-    b->sample_name_off[r + 1] = b->sample_name_off[r] + (int32_t)c.size();
-  }
-  for (int64_t i = 0; i < nsplit; i++) b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
-  b->part_offset[nsplit] = n;
-  b->n_gq_host = ctx->gt_nhost;
+  pack_names(ctx->vcf_samples, b->sample_name_off, b->sample_names);
+  fill_part_offsets(ctx, n, b->part_offset, nullptr);
   *out = b;
   return 0;
 }
@@ -4487,9 +4558,9 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
   unsigned long long* d_scal = ctx->i_scal.as<unsigned long long>();
   int32_t* d_width = (int32_t*)(d_scal + 8);
   HIPCHK(hipMemcpy(d_scal, &h, sizeof h, hipMemcpyHostToDevice));
-  HIPCHK(hipEventRecord(ctx->ev[16], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_INFO_CHECK], s));
   dq::launch_info_check(in, d_scal, d_width, s);
-  HIPCHK(hipEventRecord(ctx->ev[17], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_INFO_CHECK + 1], s));
   HIPCHK(hipMemcpyAsync(&h, d_scal, sizeof h, hipMemcpyDeviceToHost, s));  // one download
   HIPCHK(hipStreamSynchronize(s));
   if (h.sc[0] != ~0ull) {
@@ -4531,9 +4602,9 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
                          ctx->i_len.as<int32_t>(),   ctx->i_ival.as<int32_t>(), nival,
                          ctx->i_fval.as<uint64_t>(), nfval,
                          ctx->i_meta.as<int64_t>(),  (const int32_t*)(ctx->i_meta.as<uint8_t>() + 512)};
-  HIPCHK(hipEventRecord(ctx->ev[18], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_INFO_DECODE], s));
   dq::launch_info_decode(in, out, ctx->i_fix.as<int64_t>(), nhost, d_scal, s);
-  HIPCHK(hipEventRecord(ctx->ev[19], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_INFO_DECODE + 1], s));
   // ---- Float fix-ups: the texts off the exact path, converted by strtod (normally none)
   if ((rc = host_fixups(ctx, d_scal + 2, nhost, false, ctx->i_fix.p, 5, ctx->U.as<uint8_t>(), ctx->ulen,
                         "VCF INFO decode pass", "its Float texts for the host differ from the check pass's count",
@@ -4554,7 +4625,7 @@ static int info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys) {
   ctx->info_nival = nival;
   ctx->info_nfval = nfval;
   ctx->info_nhost = nhost;
-  ctx->info_ms = n > 0 ? (double)ev_ms(ctx->ev[16], ctx->ev[17]) + (double)ev_ms(ctx->ev[18], ctx->ev[19]) : 0.0;
+  ctx->info_ms = n > 0 ? pass_ms(ctx, EV_INFO_CHECK) + pass_ms(ctx, EV_INFO_DECODE) : 0.0;
   ctx->info_sig = sig;
   ctx->info_gen = ctx->text_gen;
   return 0;
@@ -4565,12 +4636,7 @@ int dq_vcf_info_run(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_sta
   ON_DEVICE(ctx);
   int rc = info_run(ctx, keys, n_keys);
   if (rc) return rc;
-  if (stats) {
-    *stats = ctx->stats;
-    stats->ms_plan += stats->ms_records;             // as dq_vcf_run
-    stats->ms_records = ctx->vcf_ms + ctx->info_ms;  // validate + decode, INFO check + decode
-    stats->ms_total += ctx->vcf_ms + ctx->info_ms;
-  }
+  text_stage_stats(ctx, ctx->vcf_ms + ctx->info_ms, stats);  // validate + decode, INFO check + decode
   return 0;
 }
 
@@ -4580,51 +4646,39 @@ int dq_vcf_info(dq_ctx* ctx, const dq_info_key* keys, int32_t n_keys, dq_info_ba
   *out = nullptr;
   int rc = info_run(ctx, keys, n_keys);
   if (rc) return rc;
-  hipStream_t s = ctx->s;
   const int64_t n = ctx->t_nkept, nsplit = (int64_t)ctx->tplans_h.size();
-  const size_t K = (size_t)n_keys, cells = K * (size_t)n, c1 = std::max<size_t>(1, cells);
+  const size_t K = (size_t)n_keys, cells = K * (size_t)n;
   const size_t nival = (size_t)ctx->info_nival, nfval = (size_t)ctx->info_nfval;
   dq_info_batch* b = (dq_info_batch*)calloc(1, sizeof(dq_info_batch));
   if (!b) return DQ_ENOMEM;
   b->n_variants = n;
   b->n_keys = n_keys;
-  b->key_type = (int32_t*)malloc(4 * K);
-  b->key_width = (int32_t*)malloc(4 * K);
-  b->key_base = (int64_t*)malloc(8 * K);
-  b->flags = (uint8_t*)malloc(c1);
-  b->n_values = (int32_t*)malloc(4 * c1);
-  b->val_off = (int32_t*)malloc(4 * c1);
-  b->val_len = (int32_t*)malloc(4 * c1);
-  b->ival = (int32_t*)malloc(4 * std::max<size_t>(1, nival));
   b->n_ival = (int64_t)nival;
-  b->fval = (double*)malloc(8 * std::max<size_t>(1, nfval));
   b->n_fval = (int64_t)nfval;
   b->n_partitions = nsplit;
-  b->part_offset = (int64_t*)malloc(8 * (size_t)(nsplit + 1));
-  if (!(b->key_type && b->key_width && b->key_base && b->flags && b->n_values && b->val_off && b->val_len &&
-        b->ival && b->fval && b->part_offset)) {
+  b->n_float_host = ctx->info_nhost;
+  HostArrays ha;
+  ha.get(K, b->key_type, b->key_width, b->key_base);
+  ha.get(cells, b->flags, b->n_values, b->val_off, b->val_len);
+  ha.get(nival, b->ival);
+  ha.get(nfval, b->fval);
+  ha.get((size_t)nsplit + 1, b->part_offset);
+  if (ha.failed) {
     dq_info_batch_free(b);
     return DQ_ENOMEM;
   }
   memcpy(b->key_type, ctx->info_type.data(), 4 * K);
   memcpy(b->key_width, ctx->info_width.data(), 4 * K);
   memcpy(b->key_base, ctx->info_base.data(), 8 * K);
-  if (cells > 0) {
-    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
-        {b->flags, ctx->i_flags.p, cells},        {b->n_values, ctx->i_nval.p, 4 * cells},
-        {b->val_off, ctx->i_off.p, 4 * cells},    {b->val_len, ctx->i_len.p, 4 * cells},
-        {b->ival, ctx->i_ival.p, 4 * nival},      {b->fval, ctx->i_fval.p, 8 * nfval}};
-    bool ok = true;
-    for (const auto& c : cp)
-      if (c.bytes) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
-      dq_info_batch_free(b);
-      RET(DQ_EDEVICE, "dq_vcf_info: device to host copy failed");
-    }
+  if (cells > 0 && (rc = download_all(ctx,
+                                      {{b->flags, ctx->i_flags.p, cells}, {b->n_values, ctx->i_nval.p, 4 * cells},
+                                       {b->val_off, ctx->i_off.p, 4 * cells}, {b->val_len, ctx->i_len.p, 4 * cells},
+                                       {b->ival, ctx->i_ival.p, 4 * nival}, {b->fval, ctx->i_fval.p, 8 * nfval}},
+                                      "dq_vcf_info"))) {
+    dq_info_batch_free(b);
+    return rc;
   }
-  for (int64_t i = 0; i < nsplit; i++) b->part_offset[i] = ctx->parts_h[(size_t)i].begin;
-  b->part_offset[nsplit] = n;
-  b->n_float_host = ctx->info_nhost;
+  fill_part_offsets(ctx, n, b->part_offset, nullptr);
   *out = b;
   return 0;
 }
@@ -4711,9 +4765,9 @@ static int tags_run(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys,
   unsigned long long* d_scal = ctx->a_scal.as<unsigned long long>();
   unsigned long long sc = ~0ull;
   HIPCHK(hipMemcpy(d_scal, &sc, 8, hipMemcpyHostToDevice));
-  HIPCHK(hipEventRecord(ctx->ev[20], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_TAG_CHECK], s));
   dq::launch_tags_check(in, d_scal, s);
-  HIPCHK(hipEventRecord(ctx->ev[21], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_TAG_CHECK + 1], s));
   HIPCHK(hipMemcpyAsync(&sc, d_scal, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (sc != ~0ull) {
@@ -4741,17 +4795,17 @@ static int tags_run(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys,
   const dq::TagCols out{ctx->a_flags.as<uint8_t>(), ctx->a_vtype.as<uint8_t>(), ctx->a_sub.as<uint8_t>(),
                         ctx->a_off.as<int32_t>(),   ctx->a_len.as<int32_t>(),   ctx->a_val.as<uint32_t>(),
                         nval,                       ctx->a_base.as<int64_t>()};
-  HIPCHK(hipEventRecord(ctx->ev[22], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_TAG_DECODE], s));
   dq::launch_tags_decode(in, out, s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->ev[23], s));
+  HIPCHK(hipEventRecord(ctx->ev[EV_TAG_DECODE + 1], s));
   HIPCHK(hipStreamSynchronize(s));
   ctx->tag_n = n;
   ctx->tag_nval = nval;
   ctx->tag_type = types;
   ctx->tag_base = base;
   ctx->tag_bounds = bounds;
-  ctx->tag_ms = n > 0 ? (double)ev_ms(ctx->ev[20], ctx->ev[21]) + (double)ev_ms(ctx->ev[22], ctx->ev[23]) : 0.0;
+  ctx->tag_ms = n > 0 ? pass_ms(ctx, EV_TAG_CHECK) + pass_ms(ctx, EV_TAG_DECODE) : 0.0;
   return 0;
 }
 
@@ -4774,45 +4828,34 @@ int dq_tags(dq_ctx* ctx, const dq_traversal* tr, const dq_tag_key* keys, int32_t
   *out = nullptr;
   int rc = tags_run(ctx, tr, keys, n_keys);
   if (rc) return rc;
-  hipStream_t s = ctx->s;
   const int64_t n = ctx->tag_n, np = (int64_t)ctx->tag_bounds.size() - 1;
-  const size_t K = (size_t)n_keys, cells = K * (size_t)n, c1 = std::max<size_t>(1, cells);
+  const size_t K = (size_t)n_keys, cells = K * (size_t)n;
   const size_t nval = (size_t)ctx->tag_nval;
   dq_tag_batch* b = (dq_tag_batch*)calloc(1, sizeof(dq_tag_batch));
   if (!b) return DQ_ENOMEM;
   b->n_records = n;
   b->n_keys = n_keys;
-  b->key_type = (int32_t*)malloc(4 * K);
-  b->key_base = (int64_t*)malloc(8 * K);
-  b->flags = (uint8_t*)malloc(c1);
-  b->vtype = (uint8_t*)malloc(c1);
-  b->subtype = (uint8_t*)malloc(c1);
-  b->val_off = (int32_t*)malloc(4 * c1);
-  b->val_len = (int32_t*)malloc(4 * c1);
-  b->val = (uint32_t*)malloc(4 * std::max<size_t>(1, nval));
   b->n_val = (int64_t)nval;
   b->n_partitions = np;
-  b->part_offset = (int64_t*)malloc(8 * (size_t)(np + 1));
-  if (!(b->key_type && b->key_base && b->flags && b->vtype && b->subtype && b->val_off && b->val_len && b->val &&
-        b->part_offset)) {
+  HostArrays ha;
+  ha.get(K, b->key_type, b->key_base);
+  ha.get(cells, b->flags, b->vtype, b->subtype, b->val_off, b->val_len);
+  ha.get(nval, b->val);
+  ha.get((size_t)np + 1, b->part_offset);
+  if (ha.failed) {
     dq_tag_batch_free(b);
     return DQ_ENOMEM;
   }
   memcpy(b->key_type, ctx->tag_type.data(), 4 * K);
   memcpy(b->key_base, ctx->tag_base.data(), 8 * K);
   memcpy(b->part_offset, ctx->tag_bounds.data(), 8 * (size_t)(np + 1));
-  if (cells > 0) {
-    const struct { void* dst; const void* src; size_t bytes; } cp[] = {
-        {b->flags, ctx->a_flags.p, cells},       {b->vtype, ctx->a_vtype.p, cells},
-        {b->subtype, ctx->a_sub.p, cells},       {b->val_off, ctx->a_off.p, 4 * cells},
-        {b->val_len, ctx->a_len.p, 4 * cells},   {b->val, ctx->a_val.p, 4 * nval}};
-    bool ok = true;
-    for (const auto& c : cp)
-      if (c.bytes) ok = ok && hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-    if (hipStreamSynchronize(s) != hipSuccess || !ok) {
-      dq_tag_batch_free(b);
-      RET(DQ_EDEVICE, "dq_tags: device to host copy failed");
-    }
+  if (cells > 0 && (rc = download_all(ctx,
+                                      {{b->flags, ctx->a_flags.p, cells}, {b->vtype, ctx->a_vtype.p, cells},
+                                       {b->subtype, ctx->a_sub.p, cells}, {b->val_off, ctx->a_off.p, 4 * cells},
+                                       {b->val_len, ctx->a_len.p, 4 * cells}, {b->val, ctx->a_val.p, 4 * nval}},
+                                      "dq_tags"))) {
+    dq_tag_batch_free(b);
+    return rc;
   }
   *out = b;
   return 0;
@@ -4853,26 +4896,17 @@ int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) 
   if (nterm && (rc = get_i64(ctx, term + nterm - 1, &last_term))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   const int64_t nl = nterm + (last_term + 1 < ulen ? 1 : 0);
-  uint64_t fin = (uint64_t)ctx->flen << 16;
-  if (ulen > 0) {
-    std::vector<int64_t> uo((size_t)nblk), bp((size_t)nblk);
-    HIPCHK(hipMemcpy(uo.data(), ctx->uoff.p, 8 * uo.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(bp.data(), ctx->blk_pos.p, 8 * bp.size(), hipMemcpyDeviceToHost));
-    const int64_t j = (int64_t)(std::upper_bound(uo.begin(), uo.end(), ulen - 1) - uo.begin()) - 1;
-    if (j + 1 < nblk) fin = (uint64_t)bp[(size_t)j + 1] << 16;
-  }
+  uint64_t fin = 0;
+  if ((rc = final_pointer_at(ctx, ulen, &fin))) return rc;
   if (nl > INT32_MAX) RET(DQ_EINVAL, "dq_text_write_tbi: more than 2147483647 lines");
-  struct Ev {
-    hipEvent_t e = nullptr;
-    ~Ev() {
-      if (e) (void)hipEventDestroy(e);
-    }
-  } e0, e1;
+  Ev e0, e1;
   HIPCHK(hipEventCreate(&e0.e));
   HIPCHK(hipEventCreate(&e1.e));
   HIPCHK(hipEventRecord(e0.e, s));
   DevBuf d_flag, d_off, d_dl, d_pos, d_end, d_vs, d_ve, d_head, d_st, d_key, d_meta, d_nfirst,
-      d_nline, d_nstart, d_nlen, d_noff, d_names, d_woff, d_lin, d_in, d_sc, d_perm, d_chunks, d_bins;
+      d_nline, d_nstart, d_nlen, d_noff, d_names;
+  BinIndex B;
+  DevBuf& d_sc = B.d_sc;  // the run numbering's scan, then the index build's
   // the compacted list of data lines
   int64_t n = 0;
   if (nl > 0) {
@@ -4962,101 +4996,30 @@ int dq_text_write_tbi(dq_ctx* ctx, uint8_t** out, int64_t* out_len, double* ms) 
       default: RET(DQ_EFORMAT, "not sorted: " + at);
     }
   }
-  // from here on as dq_write_bai: linear index, level partition, heads, emit
+  // the .bai kernels over the lines: linear index, level partition, heads, emit
   std::vector<int64_t> woff((size_t)nrun + 1, 0);
   for (int64_t r = 0; r < nrun; r++) woff[(size_t)r + 1] = woff[(size_t)r] + (int64_t)meta[5 * (size_t)r + 4];
-  const int64_t nwin = woff[(size_t)nrun];
-  int64_t nchunk = 0, nbin = 0;
-  std::vector<uint64_t> lin((size_t)nwin), chunks, bins;
-  if (n > 0) {
-    const uint64_t* voff = d_vs.as<uint64_t>();
-    const uint64_t* vend = d_ve.as<uint64_t>();
-    HIPCHK(d_woff.ensure(8 * woff.size()));
-    HIPCHK(d_lin.ensure(8 * (size_t)std::max<int64_t>(1, nwin)));
-    HIPCHK(hipMemcpyAsync(d_woff.p, woff.data(), 8 * woff.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_lin.p, 0xff, 8 * (size_t)nwin, s));
-    launch_bai_linear(d_key.as<uint64_t>(), d_end.as<int32_t>(), d_pos.as<int32_t>(), voff, n,
-                      d_woff.as<int64_t>(), nwin, d_lin.as<unsigned long long>(), s);
-    HIPCHK(d_in.ensure(8 * (size_t)n));
-    HIPCHK(d_perm.ensure(8 * (size_t)n));
-    int64_t base = 0;
-    for (int la = 0; la < 6; la += 2) {
-      launch_bai_level_flags(d_key.as<uint64_t>(), n, la, d_in.as<int64_t>(), s);
-      launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
-      int64_t tot = 0;
-      if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
-      const int64_t a = tot & 0xffffffff, b = tot >> 32;
-      launch_bai_level_scatter(d_key.as<uint64_t>(), n, la, d_sc.as<int64_t>(), base, base + a, n,
-                               d_perm.as<int64_t>(), s);
-      base += a + b;
-    }
-    if (base != n) RET(DQ_EDEVICE, "dq_text_write_tbi: level partition lost lines");
-    launch_bai_heads(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), n, d_in.as<int64_t>(), s, vend);
-    launch_exclusive_scan_i64(d_in.as<int64_t>(), d_sc.as<int64_t>(), n, ctx->tmp.as<int64_t>(), s);
-    int64_t tot = 0;
-    if ((rc = get_i64(ctx, d_sc.as<int64_t>() + n, &tot))) return rc;
-    nchunk = tot & 0xffffffff;
-    nbin = tot >> 32;
-    HIPCHK(d_chunks.ensure(16 * (size_t)nchunk));
-    HIPCHK(d_bins.ensure(16 * (size_t)nbin));
-    launch_bai_emit(d_key.as<uint64_t>(), voff, n, fin, d_perm.as<int64_t>(), n, d_in.as<int64_t>(),
-                    d_sc.as<int64_t>(), nchunk, nbin, d_chunks.as<uint64_t>(), d_bins.as<uint64_t>(), s,
-                    vend);
-    chunks.resize(2 * (size_t)nchunk);
-    bins.resize(2 * (size_t)nbin);
-    HIPCHK(hipMemcpyAsync(chunks.data(), d_chunks.p, 8 * chunks.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(bins.data(), d_bins.p, 8 * bins.size(), hipMemcpyDeviceToHost, s));
-    if (nwin) HIPCHK(hipMemcpyAsync(lin.data(), d_lin.p, 8 * lin.size(), hipMemcpyDeviceToHost, s));
-  }
+  if ((rc = build_bin_index(ctx, d_key.as<uint64_t>(), d_end.as<int32_t>(), d_pos.as<int32_t>(), d_vs.as<uint64_t>(),
+                            d_ve.as<uint64_t>(), n, n, fin, woff, "dq_text_write_tbi", "lines", &B)))
+    return rc;
   HIPCHK(hipEventRecord(e1.e, s));
   HIPCHK(hipStreamSynchronize(s));
   if (ms) *ms = ev_ms(e0.e, e1.e);
   // htsjdk TabixIndex.write: magic, n_ref, the VCF format (flags 2, sequence column 1, begin
   // column 2, end column 0, meta '#', skip 0), the names, then the .bai layout per contig with
   // neither pseudo-bin nor trailing count
-  std::vector<int64_t> order((size_t)nbin);
-  for (int64_t b = 0; b < nbin; b++) order[(size_t)b] = b;
-  std::sort(order.begin(), order.end(),
-            [&](int64_t x, int64_t y) { return bins[2 * (size_t)x] < bins[2 * (size_t)y]; });
   std::vector<uint8_t> o;
-  auto p32 = [&](uint32_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
-  auto p64 = [&](uint64_t v) { o.insert(o.end(), (uint8_t*)&v, (uint8_t*)&v + 8); };
   o.insert(o.end(), {'T', 'B', 'I', 1});
-  p32((uint32_t)nrun);
-  for (uint32_t v : {2u, 1u, 2u, 0u, (uint32_t)'#', 0u}) p32(v);
+  p32(o, (uint32_t)nrun);
+  for (uint32_t v : {2u, 1u, 2u, 0u, (uint32_t)'#', 0u}) p32(o, v);
   size_t l_nm = 0;
   for (const std::string& nm : names) l_nm += nm.size() + 1;
-  p32((uint32_t)l_nm);
+  p32(o, (uint32_t)l_nm);
   for (const std::string& nm : names) {
     o.insert(o.end(), nm.begin(), nm.end());
     o.push_back(0);
   }
-  size_t bi = 0;
-  for (int64_t r = 0; r < nrun; r++) {
-    size_t bj = bi;
-    while (bj < order.size() && (int64_t)(bins[2 * (size_t)order[bj]] >> 16) == r) bj++;
-    p32((uint32_t)(bj - bi));
-    for (; bi < bj; bi++) {
-      const int64_t b = order[bi];
-      const int64_t c0 = (int64_t)bins[2 * (size_t)b + 1];
-      const int64_t c1 = b + 1 < nbin ? (int64_t)bins[2 * (size_t)b + 3] : nchunk;
-      p32((uint32_t)(bins[2 * (size_t)b] & 0xffff));
-      p32((uint32_t)(c1 - c0));
-      for (int64_t c = c0; c < c1; c++) {
-        p64(chunks[2 * (size_t)c]);
-        p64(chunks[2 * (size_t)c + 1]);
-      }
-    }
-    // linear index: an untouched window takes the previous window's offset (leading ones stay 0)
-    const int64_t ni = woff[(size_t)r + 1] - woff[(size_t)r];
-    p32((uint32_t)ni);
-    uint64_t prev = 0;
-    for (int64_t w = 0; w < ni; w++) {
-      const uint64_t v = lin[(size_t)(woff[(size_t)r] + w)];
-      if (v != ~0ull) prev = v;
-      p64(prev);
-    }
-  }
+  put_bin_index(o, B, woff, nullptr);
   uint8_t* b = (uint8_t*)malloc(std::max<size_t>(1, o.size()));
   if (!b) return DQ_ENOMEM;
   memcpy(b, o.data(), o.size());

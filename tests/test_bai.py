@@ -235,11 +235,33 @@ def _header_only(anysam):
     return bamutil.bgzf(u[:bamutil.header_len(u)], 5)
 
 
+def _small(name, bam1):
+    """The smallest inputs of the index build, with the restated index and its parse: records but
+    none with a position ("unplaced3"), and one record with a position ("one_placed")."""
+    mk = bamutil.make_record
+    recs = {"unplaced3": [mk(-1, -1, b"u%d" % i, 50, flag=4) for i in range(3)],
+            "one_placed": [mk(0, 1000, b"r0", 50)]}[name]
+    data = _bam_of(bam1, recs)
+    want = baiutil.build_bai(data)
+    return data, want, baiutil.parse_bai(want)
+
+
+def test_restatement_small_inputs(bam1):
+    refs, nc = _small("unplaced3", bam1)[2]
+    assert nc == 3 and all(not r["bins"] and not r["linear"] and r["meta"] is None for r in refs)
+    refs, nc = _small("one_placed", bam1)[2]
+    assert nc == 0 and [i for i, r in enumerate(refs) if r["meta"] is not None] == [0]
+    assert list(refs[0]["bins"]) == [baiutil.reg2bin(1000, 1050)] and refs[0]["meta"][1] == (1, 0)
+    assert len(refs[0]["bins"][baiutil.reg2bin(1000, 1050)]) == 1 and len(refs[0]["linear"]) == 1
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["1.bam", "hiseq", "anysam", "wgs", "multiref", "longread",
-                                  "header_only"])
+                                  "header_only", "unplaced3", "one_placed"])
 def test_gpu_bai_equals_restatement(name, bam1, hiseq, anysam, wgs, multiref, restated):
-    if name == "longread":   # records over many windows and BGZF blocks, high-level bins
+    if name in ("unplaced3", "one_placed"):   # what they reach: test_restatement_small_inputs
+        data, want, _ = _small(name, bam1)
+    elif name == "longread":   # records over many windows and BGZF blocks, high-level bins
         data = synth.generate(60, seed=5, shape=synth.LONGREAD).bam
         want = baiutil.build_bai(data)
         refs, _ = baiutil.parse_bai(want)

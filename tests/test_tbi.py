@@ -88,6 +88,9 @@ def inputs():
         "header_only": T.bgzf_text(b"\n".join(HEAD) + b"\n"),
         "wide": T.bgzf_text(wide_text(), block_u=1000),
         "levels": T.bgzf_text(levels_text(), block_u=120),
+        "one_line": T.bgzf_text(b"\n".join(HEAD + [vcf_line(b"chr1", 1000)]) + b"\n"),
+        "eof_only": B.EOF_BLOCK,
+        "two_eof_blocks": d700 + B.EOF_BLOCK,
     }
 
 
@@ -195,6 +198,21 @@ def test_rules_the_fixture_does_not_reach():
     assert any(O.vcf_overlaps(l, seeded_intervals()[:-1]) for l in lines)
 
 
+def test_restatement_smallest_inputs():
+    """One data line; no decompressed byte at all; two empty blocks behind the last line, where the
+    final pointer is the first of them."""
+    p = TU.parse_tbi(restated("one_line"))
+    assert len(TU.records(inputs()["one_line"])) == 1 and p["names"] == [b"chr1"]
+    assert len(p["refs"][0]["bins"]) == 1 and [len(c) for c in p["refs"][0]["bins"].values()] == [1]
+    assert gzip.decompress(inputs()["eof_only"]) == b"" and len(inputs()["eof_only"]) == 28
+    assert restated("eof_only") == restated("header_only") and len(restated("eof_only")) == 36
+    two, one = inputs()["two_eof_blocks"], inputs()["syn700"]
+    assert two.endswith(2 * B.EOF_BLOCK) and not one.endswith(2 * B.EOF_BLOCK)
+    first_eof = len(one) - len(B.EOF_BLOCK)
+    assert TU.records(two)[-1][2] == first_eof << 16 == TU.records(one)[-1][2]
+    assert restated("two_eof_blocks") == restated("syn700")
+
+
 @pytest.mark.parametrize("name", ["pos_down", "contig_back", "pos_not_numeric", "end_too_far"])
 def test_restatement_errors(name):
     data, k = error_inputs()[name]
@@ -227,7 +245,7 @@ def text_lines(c):
 @gpu
 @pytest.mark.parametrize("name", ["hiseq", "test", "syn300", "syn700", "syn8000", "crlf", "gaps",
                                   "no_last_terminator", "no_eof_block", "header_only", "wide",
-                                  "levels"])
+                                  "levels", "one_line", "eof_only"])
 def test_gpu_tbi_equals_restatement(name):
     from disq_amd import _lib
     data, want = inputs()[name], restated(name)
@@ -255,6 +273,18 @@ def test_gpu_tbi_equals_restatement(name):
         c.text_set_index(T.whole_file_tabix(["chr1"], len(data)))
         c.text_set_intervals([("chr1", 1, 2)])
         assert c.text_write_tbi() == want
+
+
+@gpu
+def test_gpu_tbi_two_trailing_empty_blocks():
+    """The final pointer with two empty blocks behind the last line (what the input reaches:
+    test_restatement_smallest_inputs).  The index only: the text run itself takes no empty block
+    before the stream's last one, so the reads of test_gpu_tbi_equals_restatement do not apply."""
+    from disq_amd import _lib
+    with _lib.Context(split_size=0, verify_crc=True) as c:
+        c.text_open_bytes(inputs()["two_eof_blocks"])
+        assert c.text_write_tbi() == restated("two_eof_blocks")
+        assert c.text_write_tbi() == restated("two_eof_blocks")
 
 
 @gpu
