@@ -236,9 +236,14 @@ struct dq_ctx {
   // encoded records
   const uint8_t* rec_src() const { return sam_mode ? sam_rec.as<uint8_t>() : U.as<uint8_t>(); }
   // kernel 1
-  DevBuf slots, counts, offs, cand, flags, voff, scal, tmp;
-  DevBuf scan_over, scan_map, scan_big;  // second scan pass (dense BGZF regions)
-  int64_t ncand = 0;
+  DevBuf slots, counts, offs, cand, scal, tmp;
+  DevBuf scan_over, scan_map, scan_big;  // the full scan's second pass (dense BGZF regions); scan_big
+                                         // also holds the listed chunks' slots
+  DevBuf cwins, cwcnt, cwbase, cwhops;  // chain windows, their block counts, the counts' scan, recorded hops
+  // the planners' candidates: the listed chunks, the byte ranges they cover (split_cands)
+  DevBuf cand_list, cand_rng;
+  std::vector<int32_t> cand_list_h;
+  std::vector<int64_t> cand_rng_h;
   // chain + inflate
   DevBuf blk_pos, blk_cs, blk_us, uoff, status, U;
   DevBuf tails;  // inflate: the tail descriptors and header records (INFLATE_SCRATCH_BYTES per block)
@@ -879,30 +884,17 @@ void text_stage_stats(const dq_ctx* ctx, double extra_ms, dq_stats* stats) {
 
 }  // namespace
 
-// ------------------------------------------------------------------ pipeline
-static int run_pipeline(dq_ctx* ctx) {
-  if (ctx->sam_mode) RET(DQ_EINVAL, "a SAM context (dq_sam_open_*) takes the dq_sam_* calls only");
-  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
-  if (ctx->have_pipeline) return 0;
-  ctx->span_parts_valid = false;
+// ------------------------------------------------------------------ planner candidates
+// Every magic position of the file, sorted, in ctx->cand (*d_ncand of them): the scan over all
+// 16 KiB chunks, with a second pass over the chunks that hold more than SCAN_CAP.
+static int full_scan_cands(dq_ctx* ctx, int64_t* d_ncand) {
   hipStream_t s = ctx->s;
   const int64_t L = ctx->flen;
   int rc;
-  HIPCHK(hipEventRecord(ctx->ev[0], s));
-  // ---- Kernel 1: candidate scan
   const int64_t nch = std::max<int64_t>(1, (L + SCAN_CHUNK - 1) / SCAN_CHUNK);
   if ((rc = ensure_all(ctx, ctx->slots, sizeof(Cand) * (size_t)nch * SCAN_CAP))) return rc;
   if ((rc = ensure_all(ctx, ctx->counts, sizeof(int32_t) * (size_t)nch))) return rc;
   if ((rc = ensure_all(ctx, ctx->offs, sizeof(int64_t) * (size_t)(nch + 1)))) return rc;
-  if ((rc = ensure_all(ctx, ctx->tmp, sizeof(int64_t) * (size_t)(4 * (nch / 1024 + 1) + 4096 +
-                                                                 4 * (L / 65536 / 1024 + 1)))))
-    return rc;
-  if ((rc = ensure_all(ctx, ctx->scal, 4096))) return rc;
-  int32_t* d_overflow = ctx->scal.as<int32_t>();
-  int32_t* d_broken = d_overflow + 1;
-  int32_t* d_stat = d_overflow + 2;
-  int64_t* d_nblk = reinterpret_cast<int64_t*>(ctx->scal.as<char>() + 64);
-  HIPCHK(hipMemsetAsync(ctx->scal.p, 0, 4096, s));
   if ((rc = ensure_all(ctx, ctx->scan_over, sizeof(int32_t) * (size_t)(1 + SCAN_OVER_MAX)))) return rc;
   HIPCHK(hipMemsetAsync(ctx->scan_over.p, 0, sizeof(int32_t), s));
   launch_bgzf_scan(ctx->cbuf(), L, L, ctx->slots.as<Cand>(), 0, ctx->counts.as<int32_t>(),
@@ -934,76 +926,176 @@ static int run_pipeline(dq_ctx* ctx) {
     if ((rc = get_i64(ctx, ctx->offs.as<int64_t>() + nch, &ncand))) return rc;
   }
   dbg(s, "scan", nch, n_over);
-  ctx->ncand = ncand;
   const int64_t capc = std::max<int64_t>(1, ncand);
   if ((rc = ensure_all(ctx, ctx->cand, sizeof(Cand) * (size_t)capc))) return rc;
-  if ((rc = ensure_all(ctx, ctx->flags, sizeof(int32_t) * (size_t)capc))) return rc;
-  if ((rc = ensure_all(ctx, ctx->voff, sizeof(int64_t) * (size_t)(capc + 1)))) return rc;
-  launch_gather_slots(ctx->slots.as<Cand>(), ctx->counts.as<int32_t>(), ctx->offs.as<int64_t>(), nch,
-                      ctx->cand.as<Cand>(), capc, n_over > 0 ? ctx->scan_map.as<int32_t>() : nullptr,
+  launch_gather_slots(ctx->slots.as<Cand>(), SCAN_CAP, ctx->counts.as<int32_t>(), ctx->offs.as<int64_t>(),
+                      nch, ctx->cand.as<Cand>(), capc, n_over > 0 ? ctx->scan_map.as<int32_t>() : nullptr,
                       ctx->scan_big.as<Cand>(), s);
-  // ncand on device for the kernels that need it
-  int64_t* d_ncand = d_nblk + 1;
-  HIPCHK(hipMemcpyAsync(d_ncand, &ncand, sizeof(int64_t), hipMemcpyHostToDevice, s));
-  launch_valid_flags(ctx->cand.as<Cand>(), d_ncand, capc, ctx->flags.as<int32_t>(), s);
-  if ((rc = ensure_scan(ctx, ncand))) return rc;
-  launch_exclusive_scan_i32(ctx->flags.as<int32_t>(), ctx->voff.as<int64_t>(), ncand,
+  HIPCHK(hipMemcpyAsync(d_ncand, ctx->offs.as<int64_t>() + nch, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// The candidate list the planners walk BgzfBlockGuesser's loop over, for these splits.  Every
+// position the loop visits from a split start s lies before the first chain block at or after s,
+// at most 65536 bytes on, so only the chunks of [s, s + DQ_CAND_SPAN + SCAN_CHUNK) are scanned,
+// SCAN_CAP_BIG slots each; the planners are told the ranges and raise *cl->need_full when they
+// would need a position outside them (dqc::cand_next), and so does a listed chunk with more
+// positions than slots.  full (that retry, or too many listed chunks to be worth it): the scan of
+// the whole file.
+#ifndef DQ_CAND_SPAN
+#define DQ_CAND_SPAN 65536
+#endif
+static int split_cands(dq_ctx* ctx, const std::vector<std::pair<int64_t, int64_t>>& splits, bool full,
+                       CandList* cl) {
+  hipStream_t s = ctx->s;
+  const int64_t L = ctx->flen;
+  int rc;
+  int64_t* d_ncand = reinterpret_cast<int64_t*>(ctx->scal.as<char>() + 64) + 1;
+  int32_t* d_need = reinterpret_cast<int32_t*>(ctx->scal.as<char>() + 200);
+  HIPCHK(hipMemsetAsync(d_need, 0, sizeof(int32_t), s));
+  const int64_t nch = std::max<int64_t>(1, (L + SCAN_CHUNK - 1) / SCAN_CHUNK);
+  std::vector<int64_t>& rng = ctx->cand_rng_h;
+  std::vector<int32_t>& list = ctx->cand_list_h;
+  rng.clear();
+  list.assign(1, 0);
+  if (!full) {
+    std::vector<int64_t> st;
+    for (const auto& sp : splits)
+      if (sp.first < L) st.push_back(std::max<int64_t>(0, sp.first));
+    std::sort(st.begin(), st.end());
+    for (const int64_t s0 : st) {
+      const int64_t b = s0 / SCAN_CHUNK * SCAN_CHUNK;
+      const int64_t e = std::min(L, (s0 + DQ_CAND_SPAN + 2 * (int64_t)SCAN_CHUNK - 1) / SCAN_CHUNK * SCAN_CHUNK);
+      if (!rng.empty() && b <= rng.back()) {
+        rng.back() = std::max(rng.back(), e);
+      } else {
+        rng.push_back(b);
+        rng.push_back(e);
+      }
+    }
+    int64_t n = 0;
+    for (size_t r = 0; r < rng.size(); r += 2) n += (rng[r + 1] - rng[r] + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    // the listed chunks take 40 times a plain chunk's slots: past that the full scan is smaller
+    if (n > std::max<int64_t>(4096, nch / 40)) full = true;
+  }
+  *cl = CandList{nullptr, d_ncand, nullptr, 0, L, d_need};
+  if (full) {
+    if ((rc = full_scan_cands(ctx, d_ncand))) return rc;
+    cl->cand = ctx->cand.as<Cand>();
+    return 0;
+  }
+  for (size_t r = 0; r < rng.size(); r += 2)
+    for (int64_t c = rng[r] / SCAN_CHUNK; c * SCAN_CHUNK < rng[r + 1]; c++) list.push_back((int32_t)c);
+  const int64_t n = (int64_t)list.size() - 1;
+  list[0] = (int32_t)n;
+  const int64_t n1 = std::max<int64_t>(1, n);
+  if ((rc = ensure_all(ctx, ctx->cand_list, sizeof(int32_t) * (size_t)(n1 + 1)))) return rc;
+  if ((rc = ensure_all(ctx, ctx->cand_rng, sizeof(int64_t) * std::max<size_t>(2, rng.size())))) return rc;
+  if ((rc = ensure_all(ctx, ctx->scan_big, sizeof(Cand) * (size_t)n1 * SCAN_CAP_BIG))) return rc;
+  if ((rc = ensure_all(ctx, ctx->cand, sizeof(Cand) * (size_t)n1 * SCAN_CAP_BIG))) return rc;
+  if ((rc = ensure_all(ctx, ctx->counts, sizeof(int32_t) * (size_t)n1))) return rc;
+  if ((rc = ensure_all(ctx, ctx->offs, sizeof(int64_t) * (size_t)(n1 + 1)))) return rc;
+  if ((rc = ensure_scan(ctx, n1))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->cand_list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, s));
+  if (!rng.empty())
+    HIPCHK(hipMemcpyAsync(ctx->cand_rng.p, rng.data(), sizeof(int64_t) * rng.size(), hipMemcpyHostToDevice, s));
+  launch_bgzf_scan_listed(ctx->cbuf(), L, L, ctx->scan_big.as<Cand>(), n, ctx->counts.as<int32_t>(),
+                          ctx->cand_list.as<int32_t>(), nullptr, s);
+  launch_exclusive_scan_i32(ctx->counts.as<int32_t>(), ctx->offs.as<int64_t>(), n,
                             ctx->tmp.as<int64_t>(), s);
-  const int64_t capb = std::max<int64_t>(1, ncand);
+  launch_gather_slots(ctx->scan_big.as<Cand>(), SCAN_CAP_BIG, ctx->counts.as<int32_t>(),
+                      ctx->offs.as<int64_t>(), n, ctx->cand.as<Cand>(), n1 * SCAN_CAP_BIG, nullptr, nullptr, s);
+  HIPCHK(hipMemcpyAsync(d_ncand, ctx->offs.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  cl->cand = ctx->cand.as<Cand>();
+  cl->rng = ctx->cand_rng.as<int64_t>();
+  cl->nrng = (int64_t)rng.size() / 2;
+  return 0;
+}
+// After the planners' results are back: true when they must run again over the full scan.
+static bool cands_need_full(const CandList& cl, int32_t need_full, int32_t listed0) {
+  return cl.rng != nullptr && (need_full != 0 || listed0 < 0);
+}
+
+// The emit pass of Kernel 1: 1 = from the member sizes the count pass recorded, 0 = a second walk
+// (A/B in profiles/r11b_chain_window_sweep.txt).
+#ifndef DQ_CHAIN_EMIT_REC
+#define DQ_CHAIN_EMIT_REC 1
+#endif
+
+// ------------------------------------------------------------------ pipeline
+static int run_pipeline(dq_ctx* ctx) {
+  if (ctx->sam_mode) RET(DQ_EINVAL, "a SAM context (dq_sam_open_*) takes the dq_sam_* calls only");
+  if (!ctx->have_file) RET(DQ_EINVAL, "no file open");
+  if (ctx->have_pipeline) return 0;
+  ctx->span_parts_valid = false;
+  hipStream_t s = ctx->s;
+  const int64_t L = ctx->flen;
+  int rc;
+  HIPCHK(hipEventRecord(ctx->ev[0], s));
+  // ---- Kernel 1: the block chain, walked by windows from the chain start (dq_chain_core.h)
+  if ((rc = ensure_all(ctx, ctx->scal, 4096))) return rc;
+  int32_t* d_broken = ctx->scal.as<int32_t>() + 1;
+  int32_t* d_stat = ctx->scal.as<int32_t>() + 2;
+  int64_t* d_nblk = reinterpret_cast<int64_t*>(ctx->scal.as<char>() + 64);
+  unsigned long long* d_cstart = reinterpret_cast<unsigned long long*>(ctx->scal.as<char>() + 208);
+  unsigned long long* d_tot = d_cstart + 1;  // block count, sum of ISIZE
+  HIPCHK(hipMemsetAsync(ctx->scal.p, 0, 4096, s));
+  // a shard's bytes end inside the file: the end of the buffer is not EOF
+  const int32_t is_eof = (!ctx->shard || ctx->base + L >= ctx->file_len) ? 1 : 0;
+  // The chain must start at the file start (htsjdk reads from block 0); a shard's chain starts
+  // at the guesser's first block in its first split (the first position the guesser returns).
+  launch_chain_start(ctx->cbuf(), L, ctx->shard && !ctx->chunk_mode, d_cstart, s);
+  // The window is sized for about 16 k windows.  A wide window that meets members under 1 KiB on
+  // average gives up (d_dense) and the file is cut into CHAIN_W_DENSE windows instead: a second
+  // trip, for files of tiny members only.
+  int32_t* d_dense = reinterpret_cast<int32_t*>(ctx->scal.as<char>() + 232);
+  int64_t W = dqc::chain_window(L), nwin = 0;
+  uint16_t* hops = nullptr;
+  unsigned long long tot[2] = {0, 0};
+  int32_t broken = 0;
+  for (;;) {
+    const bool may_give_up = W > dqc::CHAIN_W_DENSE;
+    nwin = std::max<int64_t>(1, (L + W - 1) / W);
+    if ((rc = ensure_all(ctx, ctx->cwins, sizeof(ChainWin) * (size_t)nwin))) return rc;
+    if ((rc = ensure_all(ctx, ctx->cwcnt, sizeof(int32_t) * (size_t)nwin))) return rc;
+    if ((rc = ensure_all(ctx, ctx->cwbase, sizeof(int64_t) * (size_t)(nwin + 1)))) return rc;
+    if ((rc = ensure_scan(ctx, nwin))) return rc;
+#if DQ_CHAIN_EMIT_REC
+    if ((rc = ensure_all(ctx, ctx->cwhops, sizeof(uint16_t) * CHAIN_HOPS * (size_t)nwin))) return rc;
+    hops = ctx->cwhops.as<uint16_t>();
+#endif
+    launch_chain_windows(ctx->cbuf(), L, d_cstart, ctx->cwins.as<ChainWin>(), nwin, W,
+                         may_give_up ? d_dense : nullptr, hops, d_broken, ctx->cwcnt.as<int32_t>(), d_tot, s);
+    launch_exclusive_scan_i32(ctx->cwcnt.as<int32_t>(), ctx->cwbase.as<int64_t>(), nwin,
+                              ctx->tmp.as<int64_t>(), s);
+    // the block count and the decompressed length come back together, then the table is written
+    int32_t dense = 0;
+    HIPCHK(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&broken, d_broken, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&dense, d_dense, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!dense) break;
+    dbg(s, "chain dense", W, nwin);
+    W = dqc::CHAIN_W_DENSE;
+    HIPCHK(hipMemsetAsync(d_tot, 0, 16 + 4, s));  // the totals and d_dense
+    HIPCHK(hipMemsetAsync(d_broken, 0, 4, s));
+  }
+  const int64_t nblk = (int64_t)tot[0], ulen = (int64_t)tot[1];
+  const int64_t capb = std::max<int64_t>(1, nblk);
   if ((rc = ensure_all(ctx, ctx->blk_pos, sizeof(int64_t) * (size_t)capb))) return rc;
   if ((rc = ensure_all(ctx, ctx->blk_cs, sizeof(int32_t) * (size_t)capb))) return rc;
   if ((rc = ensure_all(ctx, ctx->blk_us, sizeof(int32_t) * (size_t)capb))) return rc;
-  // a shard's bytes end inside the file: the end of the buffer is not EOF
-  const int32_t is_eof = (!ctx->shard || ctx->base + L >= ctx->file_len) ? 1 : 0;
-  // blk_us zeroed past the chain: the scan below runs over all capb entries before the block count
-  // is known on the host, and its total is the decompressed length
-  HIPCHK(hipMemsetAsync(ctx->blk_us.p, 0, sizeof(int32_t) * (size_t)capb, s));
-  if (ncand > 0)
-    launch_chain2(ctx->cbuf(), L, ctx->cand.as<Cand>(), d_ncand, ncand,
-                  ctx->voff.as<int64_t>(), ctx->blk_pos.as<int64_t>(), ctx->blk_cs.as<int32_t>(),
-                  ctx->blk_us.as<int32_t>(), capb, d_nblk, d_broken, is_eof, s);
-  // The chain must start at the file start (htsjdk reads from block 0); a shard's chain starts
-  // at the guesser's first block in its first split (the first valid candidate).  The first
-  // valid candidate and the chain's first block come from a device reduction: one small copy
-  // brings them back with the block count and the broken flag.
-  unsigned long long* d_cc = reinterpret_cast<unsigned long long*>(ctx->scal.as<char>() + 128);
-  HIPCHK(hipMemsetAsync(d_cc, 0xff, 16, s));
-  if (ncand > 0)
-    launch_chain_check(ctx->cand.as<Cand>(), d_ncand, capc, ctx->blk_pos.as<int64_t>(), d_nblk, d_cc, s);
-  // block offsets in U (exclusive scan of ISIZE) over the capb candidates' slots
   if ((rc = ensure_all(ctx, ctx->uoff, sizeof(int64_t) * (size_t)(capb + 1)))) return rc;
+  if (nblk > 0)
+    launch_chain_emit(ctx->cbuf(), L, d_cstart, ctx->cwins.as<ChainWin>(), nwin, W, hops,
+                      ctx->cwbase.as<int64_t>(), ctx->blk_pos.as<int64_t>(), ctx->blk_cs.as<int32_t>(),
+                      ctx->blk_us.as<int32_t>(), capb, s);
+  else
+    HIPCHK(hipMemsetAsync(ctx->blk_us.p, 0, sizeof(int32_t), s));
+  // block offsets in U (exclusive scan of ISIZE)
   if ((rc = ensure_scan(ctx, capb))) return rc;
   launch_exclusive_scan_i32(ctx->blk_us.as<int32_t>(), ctx->uoff.as<int64_t>(), capb,
                             ctx->tmp.as<int64_t>(), s);
-  alignas(8) unsigned char sc[144];
-  int64_t ulen = 0;
-  HIPCHK(hipMemcpyAsync(sc, ctx->scal.p, sizeof sc, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&ulen, ctx->uoff.as<int64_t>() + capb, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  int64_t nblk = 0;
-  int32_t broken = 0;
-  unsigned long long minvalid = 0, p0 = 0;
-  memcpy(&broken, sc + 4, 4);
-  memcpy(&nblk, sc + 64, 8);
-  memcpy(&minvalid, sc + 128, 8);
-  memcpy(&p0, sc + 136, 8);
-  int64_t chain_start = 0;
-  if (ctx->shard && !ctx->chunk_mode && ncand > 0) chain_start = minvalid == ~0ull ? L : (int64_t)minvalid;
-  if (!broken && ncand > 0 && (int64_t)p0 != chain_start) broken = 1;
-  if (broken) {  // walk htsjdk headers from the start (false-positive or non-BC headers present)
-    int64_t capw = L / 26 + 2;
-    if ((rc = ensure_all(ctx, ctx->blk_pos, sizeof(int64_t) * (size_t)capw))) return rc;
-    if ((rc = ensure_all(ctx, ctx->blk_cs, sizeof(int32_t) * (size_t)capw))) return rc;
-    if ((rc = ensure_all(ctx, ctx->blk_us, sizeof(int32_t) * (size_t)capw))) return rc;
-    launch_chain_serial(ctx->cbuf(), L, chain_start, ctx->blk_pos.as<int64_t>(),
-                        ctx->blk_cs.as<int32_t>(), ctx->blk_us.as<int32_t>(), capw, d_nblk, d_stat, s);
-    if ((rc = get_i64(ctx, d_nblk, &nblk))) return rc;
-    if ((rc = ensure_all(ctx, ctx->uoff, sizeof(int64_t) * (size_t)(nblk + 1)))) return rc;
-    if ((rc = ensure_scan(ctx, nblk))) return rc;
-    launch_exclusive_scan_i32(ctx->blk_us.as<int32_t>(), ctx->uoff.as<int64_t>(), nblk,
-                              ctx->tmp.as<int64_t>(), s);
-    if ((rc = get_i64(ctx, ctx->uoff.as<int64_t>() + nblk, &ulen))) return rc;
-  }
   dbg(s, "chain", nblk, broken);
   ctx->nblk = nblk;
   if (nblk == 0 && L > 0) RET(DQ_EFORMAT, "no BGZF blocks found");
@@ -1152,6 +1244,32 @@ static int run_pipeline(dq_ctx* ctx) {
   const bool no_guess = ctx->index_only || ctx->sbi_plan || ctx->chunk_mode;
   if ((ctx->index_only || ctx->sbi_plan) && ctx->shard && !ctx->chunk_mode)
     RET(DQ_EINVAL, "splitting-index planning and indexing need the whole file");
+  // the guessing planners over the splits' candidate list (split_cands); their results and the
+  // list's two flags come back with the synchronisation below, which runs them again over the full
+  // scan when the listed ranges were not enough
+  const std::vector<SplitPlan> plans0 = ctx->plans_h;
+  CandList cl{};
+  int32_t cand_flags[2] = {0, 0};  // need_full, the listed chunks' count (-1: one overflowed)
+  auto guess_plans = [&](bool full) -> int {
+    int rc;
+    if ((rc = split_cands(ctx, splits, full, &cl))) return rc;
+    if (full)
+      HIPCHK(hipMemcpyAsync(ctx->plans.p, plans0.data(), sizeof(SplitPlan) * (size_t)nsplit,
+                            hipMemcpyHostToDevice, s));
+    launch_plan_blocks(cl, ctx->blk_pos.as<int64_t>(), ctx->blk_us.as<int32_t>(),
+                       ctx->uoff.as<int64_t>(), d_nblk, ctx->plans.as<SplitPlan>(), nsplit, s);
+    if ((rc = ensure_all(ctx, ctx->plan_best, 16 * (size_t)nsplit))) return rc;
+    launch_first_record(ctx->U.as<uint8_t>(), ulen, is_eof, ctx->d_ref_len.as<int32_t>(), ctx->n_ref,
+                        ctx->blk_pos.as<int64_t>(), ctx->uoff.as<int64_t>(), d_nblk,
+                        ctx->plans.as<SplitPlan>(), nsplit, ctx->plan_best.as<unsigned long long>(), s);
+    HIPCHK(hipMemcpyAsync(ctx->plans_h.data(), ctx->plans.p, sizeof(SplitPlan) * (size_t)nsplit,
+                          hipMemcpyDeviceToHost, s));
+    if (cl.rng) {
+      HIPCHK(hipMemcpyAsync(&cand_flags[0], cl.need_full, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&cand_flags[1], ctx->cand_list.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    return 0;
+  };
   if (ctx->chunk_mode) {
     // one partition: the caller's Chunk; both ends are pointers (BAMFileIndexIterator limits,
     // H/BAMFileReader2.java:1082-1095), the start must be a record start
@@ -1182,15 +1300,7 @@ static int run_pipeline(dq_ctx* ctx) {
     HIPCHK(hipMemcpyAsync(ctx->plans.p, ctx->plans_h.data(), sizeof(SplitPlan) * (size_t)nsplit,
                           hipMemcpyHostToDevice, s));
   } else {
-  launch_plan_blocks(ctx->cand.as<Cand>(), d_ncand, ctx->blk_pos.as<int64_t>(),
-                     ctx->blk_us.as<int32_t>(), ctx->uoff.as<int64_t>(), d_nblk,
-                     ctx->plans.as<SplitPlan>(), nsplit, s);
-  if ((rc = ensure_all(ctx, ctx->plan_best, 16 * (size_t)nsplit))) return rc;
-  launch_first_record(ctx->U.as<uint8_t>(), ulen, is_eof, ctx->d_ref_len.as<int32_t>(), ctx->n_ref,
-                      ctx->blk_pos.as<int64_t>(), ctx->uoff.as<int64_t>(), d_nblk,
-                      ctx->plans.as<SplitPlan>(), nsplit, ctx->plan_best.as<unsigned long long>(), s);
-  HIPCHK(hipMemcpyAsync(ctx->plans_h.data(), ctx->plans.p, sizeof(SplitPlan) * (size_t)nsplit,
-                        hipMemcpyDeviceToHost, s));
+    if ((rc = guess_plans(false))) return rc;
   }
   // block statistics (DEFLATE payload bytes, the shard's chain end and owned bytes) by a device
   // reduction, back with the same synchronisation (the block table itself stays in HBM)
@@ -1204,6 +1314,13 @@ static int run_pipeline(dq_ctx* ctx) {
   if (defer_bad) HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (bad != ~0ull) return bad_block();  // before any planning status: the inflate failed first
+  if (cands_need_full(cl, cand_flags[0], cand_flags[1])) {
+    // the first pass's plans (some abandoned half-set by a planner that raised the flag, and the
+    // record guesser's work on them) are discarded: planned again from plans0 over the full scan,
+    // at the price of a second synchronisation
+    if ((rc = guess_plans(true))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+  }
   HIPCHK(hipEventRecord(ctx->ev[3], s));
   dbg(s, "plan", nsplit);
   int64_t start_lin = ctx->chunk_mode ? ctx->plans_h[0].rec_lin : no_guess ? ctx->header_bytes : -1;
@@ -1399,7 +1516,6 @@ static int text_run(dq_ctx* ctx, int32_t drop_hash) {
   hipStream_t s = ctx->s;
   const int64_t nblk = ctx->nblk, ulen = ctx->ulen, L = ctx->flen;
   int32_t* d_stat = ctx->scal.as<int32_t>() + 2;
-  int64_t* d_ncand = reinterpret_cast<int64_t*>(ctx->scal.as<char>() + 64) + 1;
   HIPCHK(hipEventRecord(ctx->ev[2], s));
   {  // an empty block inside the stream would end a split's stream there: not reproduced
     std::vector<int32_t> us((size_t)nblk);
@@ -1459,13 +1575,25 @@ static int text_run(dq_ctx* ctx, int32_t drop_hash) {
   if ((rc = ensure_all(ctx, ctx->t_plans, sizeof(TextPlan) * (size_t)(nsplit + 1)))) return rc;
   HIPCHK(hipMemcpyAsync(ctx->t_plans.p, ctx->tplans_h.data(), sizeof(TextPlan) * (size_t)nsplit,
                         hipMemcpyHostToDevice, s));
-  launch_text_plan(ctx->cand.as<Cand>(), d_ncand, ctx->blk_pos.as<int64_t>(), ctx->blk_us.as<int32_t>(),
-                   ctx->uoff.as<int64_t>(), nblk, L, ctx->U.as<uint8_t>(), ulen,
-                   ctx->t_term.as<int64_t>(), nterm, ctx->t_crf.as<int64_t>(),
-                   ctx->t_plans.as<TextPlan>(), nsplit, s);
-  HIPCHK(hipMemcpyAsync(ctx->tplans_h.data(), ctx->t_plans.p, sizeof(TextPlan) * (size_t)nsplit,
-                        hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  // the planner over the splits' candidate list, and again over the full scan when the listed
+  // ranges were not enough (split_cands)
+  for (int full = 0; full < 2; full++) {
+    CandList cl{};
+    int32_t cand_flags[2] = {0, 0};
+    if ((rc = split_cands(ctx, splits, full != 0, &cl))) return rc;
+    launch_text_plan(cl, ctx->blk_pos.as<int64_t>(), ctx->blk_us.as<int32_t>(),
+                     ctx->uoff.as<int64_t>(), nblk, L, ctx->U.as<uint8_t>(), ulen,
+                     ctx->t_term.as<int64_t>(), nterm, ctx->t_crf.as<int64_t>(),
+                     ctx->t_plans.as<TextPlan>(), nsplit, s);
+    HIPCHK(hipMemcpyAsync(ctx->tplans_h.data(), ctx->t_plans.p, sizeof(TextPlan) * (size_t)nsplit,
+                          hipMemcpyDeviceToHost, s));
+    if (cl.rng) {
+      HIPCHK(hipMemcpyAsync(&cand_flags[0], cl.need_full, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&cand_flags[1], ctx->cand_list.p, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (!cands_need_full(cl, cand_flags[0], cand_flags[1])) break;
+  }
   HIPCHK(hipEventRecord(ctx->ev[3], s));
   int32_t bom = 0;
   std::vector<int64_t> rng(2 * (size_t)nsplit + 1);  // begin[nsplit] | out_off[nsplit + 1]

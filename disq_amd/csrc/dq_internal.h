@@ -28,7 +28,8 @@ enum : int32_t {
 // dq_checked_report (dq_api.hip) collects every unit's words after a run.  In the product build
 // DQ_CHK compiles to nothing.
 enum : int {
-  CHK_K1_SLOT = 0,   // K1: a candidate's slot outside its chunk's CAP slots
+  CHK_K1_SLOT = 0,   // K1: a candidate's slot outside its chunk's CAP slots; a chain window's block
+                     //     outside the block table
   CHK_K2_BITS = 1,   // K2: the bit reader loads a word past the member's deflate data (+ slack);
                      // the header pre-pass asks for a word outside its lane's window
   CHK_K2_IMAGE = 2,  // K2: an emit / stored-copy store outside the LDS output image
@@ -86,6 +87,7 @@ __device__ unsigned int g_dq_chk[3];
 // the name table the SAM and VCF kernels take (dqt::NameTable); a unit that wants the lookup's
 // bound counted defines DQT_CHECK before it includes this header
 #include "dq_text_core.h"
+#include "dq_chain_core.h"
 
 // ------------------------------------------------------------------ hashing
 __host__ __device__ inline uint64_t dq_mix64(uint64_t z) {
@@ -103,49 +105,55 @@ __host__ __device__ inline uint64_t dq_mix64(uint64_t z) {
 // All pointers are device pointers; all launches go on `s`.
 namespace dq {
 
-struct Cand {          // a BgzfBlockGuesser-visible magic position
-  int64_t pos;
-  int32_t csize;       // guesser cSize (BSIZE + 1 via the BC subfield)
-  int32_t usize;       // ISIZE
-  int32_t valid;       // 1 = guessNextBGZFPos would return this block; 0 = magic only
-  int32_t pad;
-};
+using dqc::Cand;      // a BgzfBlockGuesser-visible magic position (dq_chain_core.h)
+using dqc::ChainWin;
 
 constexpr int SCAN_CHUNK = 16384;  // bytes of C per scan workgroup
 constexpr int SCAN_CAP = 32;       // candidate slots per chunk in the first scan pass
 constexpr int SCAN_CAP_BIG = 640;  // slots of a re-scanned chunk (BGZF members are >= 28 bytes)
 constexpr int SCAN_OVER_MAX = 1 << 22;  // chunks the second pass can take
 
-// Kernel 1: BGZF candidate scan of C[0, n) (file offsets; L = readable bytes).  Writes each
+// Kernel 1, the block chain by windows of W bytes (dq_chain_core.h; W a multiple of 16).  The chain
+// start *d_cstart is 0, or for a shard (find_start) the first position from byte 0 that the
+// guesser returns (L if none).
+void launch_chain_start(const uint8_t* C, int64_t L, int32_t find_start, unsigned long long* d_cstart,
+                        hipStream_t s);
+// Speculate, walk and link the nwin >= ceil(L / W) windows, repair broken links, and leave
+// tot[0] = the block count, tot[1] = the sum of ISIZE; counts[w] = window w's blocks.  d_dense
+// (or nullptr): set, and the results void, when a window's members are under 1 KiB on average --
+// the caller then cuts the file into finer windows.
+void launch_chain_windows(const uint8_t* C, int64_t L, const unsigned long long* d_cstart,
+                          ChainWin* wins, int64_t nwin, int64_t W, int32_t* d_dense, uint16_t* hops,
+                          int32_t* d_broken, int32_t* counts, unsigned long long* tot, hipStream_t s);
+// The block table from the walked windows (base: exclusive scan of counts; cap entries).  hops (or
+// nullptr, in both calls): CHAIN_HOPS 16-bit member sizes per window that the count pass records and
+// the emit pass takes instead of walking again.
+constexpr int CHAIN_HOPS = 128;
+void launch_chain_emit(const uint8_t* C, int64_t L, const unsigned long long* d_cstart,
+                       const ChainWin* wins, int64_t nwin, int64_t W, const uint16_t* hops,
+                       const int64_t* base, int64_t* blk_pos, int32_t* blk_csize, int32_t* blk_usize,
+                       int64_t cap, hipStream_t s);
+
+// BGZF candidate scan of C[0, n) (file offsets; L = readable bytes) for the planners.  Writes each
 // chunk's candidates sorted into slots[chunk * SCAN_CAP ...] and its count.
 void launch_bgzf_scan(const uint8_t* C, int64_t n, int64_t L, Cand* slots, int64_t cap,
                       int32_t* chunk_counts, int64_t n_chunks, int64_t* d_count,
                       int32_t* over_list, hipStream_t s);
-// Second pass over the chunks listed in over_list[1..over_list[0]] (more than SCAN_CAP hits).
+// Pass over the n_over chunks listed in over_list[1..], SCAN_CAP_BIG slots each (over_list[0] = -1
+// when one holds more).  With over_map the count goes to chunk_counts[chunk] and
+// over_map[chunk] = the chunk's place in the list (the full scan's second pass over chunks with
+// more than SCAN_CAP hits); without, to chunk_counts[place] (the planners' listed chunks).
 void launch_bgzf_scan_listed(const uint8_t* C, int64_t n, int64_t L, Cand* big, int64_t n_over,
                              int32_t* chunk_counts, int32_t* over_list, int32_t* over_map,
                              hipStream_t s);
-void launch_gather_slots(const Cand* slots, const int32_t* counts, const int64_t* offs,
+// out[offs[ch] + i] = chunk ch's i-th candidate: from big + over_map[ch] * SCAN_CAP_BIG where
+// over_map lists it, else from slots + ch * stride.
+void launch_gather_slots(const Cand* slots, int64_t stride, const int32_t* counts, const int64_t* offs,
                          int64_t nchunks, Cand* out, int64_t cap, const int32_t* over_map,
                          const Cand* big, hipStream_t s);
-void launch_valid_flags(const Cand* cand, const int64_t* ncand, int64_t cap, int32_t* flags,
-                        hipStream_t s);
-// Chain check: valid candidates must be htsjdk blocks linked by pos + BSIZE + 1.
-void launch_chain2(const uint8_t* C, int64_t L, const Cand* cand, const int64_t* ncand, int64_t cap,
-                   const int64_t* voff, int64_t* blk_pos, int32_t* blk_csize, int32_t* blk_usize,
-                   int64_t blk_cap, int64_t* d_nblk, int32_t* d_broken, int32_t eof_in_buf,
-                   hipStream_t s);
-// out[0] = min pos of the valid candidates (out initialised to all ones), out[1] = blk_pos[0].
-void launch_chain_check(const Cand* cand, const int64_t* d_ncand, int64_t cap, const int64_t* blk_pos,
-                        const int64_t* d_nblk, unsigned long long* out, hipStream_t s);
 // out[0] = the first block index (through sel when given) whose status is not ST_OK.
 void launch_first_bad(const int32_t* status, const int32_t* sel, int64_t n, unsigned long long* out,
                       hipStream_t s);
-// Serial fallback chain walk (one lane) over htsjdk headers from `start`.
-void launch_chain_serial(const uint8_t* C, int64_t clen, int64_t start, int64_t* blk_pos,
-                         int32_t* blk_csize, int32_t* blk_usize, int64_t cap, int64_t* d_nblk,
-                         int32_t* d_status, hipStream_t s);
-
 // Exclusive prefix sums; out has n + 1 entries (out[n] = total).  tmp >= 4*ceil(n/1024)+256.
 void launch_exclusive_scan_i32(const int32_t* in, int64_t* out, int64_t n, int64_t* tmp,
                                hipStream_t s);
@@ -184,7 +192,17 @@ struct SplitPlan {
   int32_t status;        // 0 ok; 100 = needs more data; else error
   int32_t rec_span;      // bytes of the <= 10 records chained from rec_lin (segment sizing)
 };
-void launch_plan_blocks(const Cand* cand, const int64_t* d_ncand, const int64_t* blk_pos,
+// The planners' candidate list: cand[0, *d_ncand) covers the nrng byte ranges rng (nullptr: the
+// whole file); *need_full is set when a planner needs a position outside them.
+struct CandList {
+  const Cand* cand;
+  const int64_t* d_ncand;
+  const int64_t* rng;
+  int64_t nrng;
+  int64_t L;
+  int32_t* need_full;
+};
+void launch_plan_blocks(CandList cl, const int64_t* blk_pos,
                         const int32_t* blk_usize, const int64_t* uoff, const int64_t* d_nblk,
                         SplitPlan* plans, int64_t nsplit, hipStream_t s);
 void launch_guess_all(const uint8_t* U, int64_t ulen, int32_t u_is_eof, const int32_t* ref_len,
@@ -353,7 +371,7 @@ void launch_text_terms(const uint8_t* U, int64_t ulen, int32_t* tile_count, cons
                        int64_t* term_pos, bool emit, hipStream_t s);
 void launch_text_cr_fills(const uint8_t* U, const int64_t* uoff, const int32_t* blk_us, int64_t nblk,
                           int64_t* last_cr_fill, hipStream_t s);
-void launch_text_plan(const Cand* cand, const int64_t* ncand, const int64_t* blk_pos,
+void launch_text_plan(CandList cl, const int64_t* blk_pos,
                       const int32_t* blk_us, const int64_t* uoff, int64_t nblk, int64_t flen,
                       const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
                       const int64_t* last_cr_fill, TextPlan* plans, int64_t nsplit, hipStream_t s);

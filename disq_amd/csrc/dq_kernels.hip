@@ -1,6 +1,7 @@
 // dq_kernels.hip -- Kernels 1, 3, 4 and the planning kernels of the BAM read path on gfx950.
 //
-// Kernel 1  bgzf_scan / chain      replaces BgzfBlockGuesser + BgzfBlockSource
+// Kernel 1  chain_walk / bgzf_scan replaces BgzfBlockGuesser + BgzfBlockSource: the block chain by
+//           windows from the chain start, the guesser's candidates behind the split starts
 //           (D/impl/formats/bgzf/BgzfBlockGuesser.java:76-149, BgzfBlockSource.java:63-84)
 // planning  plan_blocks / first_record   replaces BamSource.getFirstReadInPartition +
 //           BamRecordGuesser (D/impl/formats/bam/BamSource.java:110-153,
@@ -47,39 +48,9 @@ __device__ unsigned long long g_rec_tim[8];
 #endif
 
 // ------------------------------------------------------------------ Kernel 1: BGZF scan
-constexpr uint32_t BGZF_MAGIC = 0x04088b1fu;
-
-// The part of BgzfBlockGuesser.guessNextBGZFPos after a magic match at q
-// (BgzfBlockGuesser.java:93-144).  Returns 1 (block), 0 (cancelled: scan resumes at q+4) or
-// 2 (an IOException: guessNextBGZFPos returns null).  L = readable bytes.
-__device__ int guesser_at(const uint8_t* C, int64_t q, int64_t L, int32_t* cs, int32_t* us) {
-  if (q + 12 > L) return 2;
-  int64_t xlen = ld16(C, q + 10);
-  int64_t p = q + 12;
-  const int64_t sub_end = p + xlen;
-  while (p < sub_end) {
-    if (p + 4 > L) return 2;
-    uint32_t id = (uint32_t)ld32(C, p);
-    if (id != 0x00024342u) {
-      p += 4 + ld16(C, p + 2);
-      continue;
-    }
-    if (p + 6 > L) return 2;
-    int64_t bsize = ld16(C, p + 4);
-    p += 6;
-    while (p < sub_end) {
-      if (p + 4 > L) return 2;
-      p += 4 + ld16(C, p + 2);
-    }
-    if (p != sub_end) return 0;
-    p += bsize - xlen - 19 + 4;
-    if (p < 0 || p + 4 > L) return 2;
-    *cs = (int32_t)(p + 4 - q);
-    *us = ld32(C, p);
-    return 1;
-  }
-  return 0;
-}
+using dqc::BGZF_MAGIC;
+using dqc::guesser_at;  // dq_chain_core.h
+using dqc::htsjdk_block;
 
 // One workgroup of 256 lanes per 16 KiB chunk; each lane tests 16 positions per step with one
 // 16-byte coalesced load (+4 look-ahead bytes).  Hits are rare and collected in LDS, then
@@ -97,6 +68,7 @@ __global__ __launch_bounds__(256) void bgzf_scan_kernel(const uint8_t* __restric
   __shared__ int32_t nh;
   const int64_t chunk = LISTED ? (int64_t)over_list[1 + blockIdx.x] : (int64_t)blockIdx.x;
   const int64_t base = chunk * SCAN_CHUNK;
+  const int64_t cnt_at = LISTED && !over_map ? (int64_t)blockIdx.x : chunk;  // the planners' list: by place
   if (threadIdx.x == 0) nh = 0;
   __syncthreads();
   for (int it = 0; it < SCAN_CHUNK / 4096; it++) {
@@ -133,7 +105,7 @@ __global__ __launch_bounds__(256) void bgzf_scan_kernel(const uint8_t* __restric
   int32_t m = nh;
   if (m > CAP) {
     if (threadIdx.x == 0) {
-      counts[chunk] = 0;
+      counts[cnt_at] = 0;
       if (LISTED) {
         over_list[0] = -1;  // more than SCAN_CAP_BIG magic positions in 16 KiB: unsupported
       } else {
@@ -153,12 +125,13 @@ __global__ __launch_bounds__(256) void bgzf_scan_kernel(const uint8_t* __restric
     slots[slot0 + rank] = c;
   }
   if (threadIdx.x == 0) {
-    counts[chunk] = m;
-    if (LISTED) over_map[chunk] = (int32_t)blockIdx.x;
+    counts[cnt_at] = m;
+    if (LISTED && over_map) over_map[chunk] = (int32_t)blockIdx.x;
   }
 }
 
-__global__ void gather_slots_kernel(const Cand* __restrict__ slots, const int32_t* __restrict__ counts,
+__global__ void gather_slots_kernel(const Cand* __restrict__ slots, int64_t stride,
+                                    const int32_t* __restrict__ counts,
                                     const int64_t* __restrict__ offs, int64_t nchunks,
                                     Cand* __restrict__ out, int64_t cap,
                                     const int32_t* __restrict__ over_map, const Cand* __restrict__ big) {
@@ -167,7 +140,7 @@ __global__ void gather_slots_kernel(const Cand* __restrict__ slots, const int32_
   int32_t m = counts[ch];
   int64_t o = offs[ch];
   const int32_t ov = over_map ? over_map[ch] : -1;
-  const Cand* src = ov >= 0 ? big + (int64_t)ov * SCAN_CAP_BIG : slots + ch * SCAN_CAP;
+  const Cand* src = ov >= 0 ? big + (int64_t)ov * SCAN_CAP_BIG : slots + ch * stride;
   for (int i = threadIdx.x; i < m; i += blockDim.x)
     if (o + i < cap) out[o + i] = src[i];
 }
@@ -218,82 +191,250 @@ void exclusive_scan(const T* in, int64_t* out, int64_t n, int64_t* tmp, hipStrea
   }
 }
 
-// ------------------------------------------------------------------ chain
-// htsjdk reads blocks one after another by BSIZE at header offset 16 and requires XLEN == 6
-// (BlockGunzipper.unzipBlock).  Valid guesser candidates must form exactly that chain.
-__device__ inline int htsjdk_block(const uint8_t* C, int64_t p, int64_t L, int32_t* cs) {
-  if (p + 18 > L) return 0;
-  if ((uint32_t)ld32(C, p) != BGZF_MAGIC || ld16(C, p + 10) != 6) return 0;
-  int32_t c = (int32_t)ld16(C, p + 16) + 1;
-  if (c < 26 || p + c > L) return 0;
-  *cs = c;
-  return 1;
+// ------------------------------------------------------------------ chain (dq_chain_core.h)
+using dqc::ChainWin;
+
+// bit k = the BGZF magic stands at off + k, k < 16: one 16-byte load and 4 look-ahead bytes
+// (C is padded by >= 64 bytes)
+__device__ inline uint32_t magic_mask16(const uint8_t* __restrict__ C, int64_t off) {
+  const uint4 v = *reinterpret_cast<const uint4*>(C + off);
+  const uint32_t nx = *reinterpret_cast<const uint32_t*>(C + off + 16);
+  const uint32_t w[5] = {v.x, v.y, v.z, v.w, nx};
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    const int wi = k >> 2, sb = (k & 3) * 8;
+    const uint32_t win = sb ? (uint32_t)((((uint64_t)w[wi + 1] << 32) | w[wi]) >> sb) : w[wi];
+    m |= (uint32_t)(win == BGZF_MAGIC) << k;
+  }
+  return m;
 }
 
-__global__ void valid_flags_kernel(const Cand* __restrict__ cand, const int64_t* __restrict__ ncand,
-                                   int32_t* __restrict__ flags) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < *ncand) flags[i] = cand[i].valid == 1;
+__device__ inline int64_t chain_start_of(const unsigned long long* d_cstart, int64_t L) {
+  const unsigned long long v = *d_cstart;
+  return v > (unsigned long long)L ? L : (int64_t)v;
 }
 
-__global__ void chain_kernel(const uint8_t* __restrict__ C, int64_t L, const Cand* __restrict__ cand,
-                             const int64_t* __restrict__ ncand, const int64_t* __restrict__ voff,
-                             int64_t* __restrict__ blk_pos, int32_t* __restrict__ blk_csize,
-                             int32_t* __restrict__ blk_usize, int64_t cap, int64_t* d_nblk,
-                             int32_t* d_broken, int32_t eof_in_buf) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t nc = *ncand;
-  int64_t nv = voff[nc];
-  if (i == 0) *d_nblk = nv;
-  if (i >= nc || cand[i].valid != 1) return;
-  int64_t k = voff[i];
-  if (k >= cap) {
-    *d_broken = 1;
+// A shard's chain start: the first position from byte 0 that the guesser returns.  CS_K workgroups
+// take interleaved 4 KiB steps; a hit goes to *best by a 64-bit atomic minimum, and a workgroup
+// stops once its next step starts past the current minimum -- every position below the final
+// minimum was tested by the workgroup that owns its step.
+constexpr int CS_K = 64;
+__global__ __launch_bounds__(256) void chain_start_kernel(const uint8_t* __restrict__ C, int64_t L,
+                                                          unsigned long long* best) {
+  for (int64_t st = blockIdx.x;; st += CS_K) {
+    const int64_t off0 = st * 4096;
+    if (off0 >= L || (unsigned long long)off0 > *(volatile unsigned long long*)best) return;
+    const int64_t off = off0 + threadIdx.x * 16;
+    if (off >= L) continue;
+    uint32_t m = magic_mask16(C, off);
+    while (m) {
+      const int64_t q = off + __builtin_ctz(m);
+      m &= m - 1;
+      int32_t cs = 0, us = 0;
+      if (q + 4 <= L && guesser_at(C, q, L, &cs, &us) == 1) {
+        atomicMin(best, (unsigned long long)q);
+        break;
+      }
+    }
+  }
+}
+
+// One wave per window.  Count pass (EMIT = false): speculate the window's first block (window 0
+// starts at the chain start exactly) with coalesced 16-byte loads, 4 KiB per step, then walk to the
+// window's end and record count, ISIZE sum, exit and stop.  Emit pass (EMIT = true): walk the
+// window's `count` blocks again from its (by now exact) start and write the table at base[w].
+// Every lane walks the same chain (the loads are wave-uniform); lane 0 stores.  A walk is a chain
+// of dependent header loads, a 128-byte line per member: where members are short (a file of empty
+// or tiny members: 37 k hops per MiB) the wave stages CHAIN_STAGE bytes in LDS and hops there.
+constexpr int CHAIN_STAGE = 4096;  // bytes staged in LDS for a dense stretch
+constexpr int CHAIN_DENSE = 1024;  // a member shorter than this: its successors are read from LDS
+// hops (or nullptr): the count pass also records the members' sizes - 1 as 16-bit values,
+// CHAIN_HOPS per window (ChainWin.pad = 1 when they all fit; a repair clears it), and the emit pass
+// of such a window takes the positions from a wave scan of them and reads the trailers in
+// parallel instead of walking the chain a second time (as seg_walk and seg_copy do for records).
+template <bool EMIT>
+__global__ __launch_bounds__(64) void chain_walk_kernel(
+    const uint8_t* __restrict__ C, int64_t L, const unsigned long long* __restrict__ d_cstart,
+    ChainWin* __restrict__ wins, int64_t nwin, int64_t W, int32_t* d_dense, uint16_t* __restrict__ hops,
+    const int64_t* __restrict__ base, int64_t* __restrict__ blk_pos,
+    int32_t* __restrict__ blk_csize, int32_t* __restrict__ blk_usize, int64_t cap) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[CHAIN_STAGE];
+  const int lane = threadIdx.x;
+  const int64_t w = blockIdx.x;
+  if (w >= nwin) return;
+  const int64_t cs0 = chain_start_of(d_cstart, L);
+  const int64_t ws = cs0 + w * W;
+  if (ws >= L) {  // no bytes: the chain cannot enter this window
+    if (!EMIT && lane == 0) wins[w] = ChainWin{-1, L, 0, 0, 0, 0};
     return;
   }
-  const Cand c = cand[i];
-  int32_t cs;
-  if (!htsjdk_block(C, c.pos, L, &cs) || cs != c.csize) {
-    *d_broken = 1;
-    return;
-  }
-  blk_pos[k] = c.pos;
-  blk_csize[k] = cs;
-  blk_usize[k] = c.usize;
-  // link to the next valid candidate
-  int64_t nextpos = -1;
-  for (int64_t j = i + 1; j < nc; j++)
-    if (cand[j].valid == 1) {
-      nextpos = cand[j].pos;
-      break;
+  const int64_t we = min(L, ws + W);
+  int64_t start = -1, left = 0, o = 0;
+  if (EMIT) {
+    start = wins[w].start;
+    left = wins[w].count;
+    o = base[w];
+    if (hops && wins[w].pad == 1) {  // recorded: 64 blocks per step, no dependent loads
+      const uint16_t* h = hops + w * CHAIN_HOPS;
+      int64_t at = start;
+      for (int64_t k0 = 0; k0 < left; k0 += 64) {
+        const int64_t k = k0 + lane;
+        const int32_t cs = k < left ? (int32_t)h[k] + 1 : 0;
+        int32_t incl = cs;
+        for (int d = 1; d < 64; d <<= 1) {
+          const int32_t t = __shfl_up(incl, d, 64);
+          if (lane >= d) incl += t;
+        }
+        const int64_t p = at + incl - cs;
+        if (k < left) DQ_CHK(o + k < cap && p + cs <= L, CHK_K1_SLOT);
+        if (k < left && o + k < cap && p + cs <= L) {
+          blk_pos[o + k] = p;
+          blk_csize[o + k] = cs;
+          blk_usize[o + k] = dqc::ld32(C, p + cs - 4);
+        }
+        at += __shfl(incl, 63, 64);
+      }
+      return;
     }
-  if (nextpos >= 0) {
-    if (c.pos + cs != nextpos) *d_broken = 1;
-  } else if (eof_in_buf && c.pos + cs != L) {
-    *d_broken = 1;
+  } else if (w == 0) {
+    start = cs0;
+  } else {
+    for (int64_t b = ws & ~(int64_t)15; b < we && start < 0; b += 4096) {
+      uint32_t m[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int64_t off = b + j * 1024 + lane * 16;
+        m[j] = off < we ? magic_mask16(C, off) : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int64_t off = b + j * 1024 + lane * 16;
+        int64_t hit = -1;
+        uint32_t mm = m[j];
+        while (mm) {
+          const int64_t q = off + __builtin_ctz(mm);
+          mm &= mm - 1;
+          if (q >= ws && q < we && q + 4 <= L && dqc::spec_at(C, q, L)) {
+            hit = q;
+            break;
+          }
+        }
+        const uint64_t bal = __ballot(hit >= 0);
+        if (bal && start < 0) start = __shfl(hit, __builtin_ctzll(bal), 64);  // lanes are in position order
+      }
+    }
+  }
+  int64_t p = start, n = 0, usum = 0;
+  int64_t sb = 0, se = 0;  // C[sb, se) is staged
+  int32_t stop = 0;
+  if (start >= 0) {
+    while (EMIT ? n < left : p < we) {
+      int32_t cs = 0;
+      const bool inl = p >= sb && p + 18 <= se;
+      const int ok = inl ? htsjdk_block(stage, p - sb, L - sb, &cs) : htsjdk_block(C, p, L, &cs);
+      if (!ok) {
+        stop = 1;
+        break;
+      }
+      const int64_t t = p + cs - 4;
+      const int32_t us = (inl && t + 4 <= se) ? dqc::ld32(stage, t - sb) : dqc::ld32(C, t);
+      if (EMIT) DQ_CHK(o + n < cap, CHK_K1_SLOT);
+      if (EMIT && lane == 0 && o + n < cap) {
+        blk_pos[o + n] = p;
+        blk_csize[o + n] = cs;
+        blk_usize[o + n] = us;
+      }
+      if (!EMIT && hops && lane == 0 && n < CHAIN_HOPS) hops[w * CHAIN_HOPS + n] = (uint16_t)(cs - 1);
+      usum += us;
+      n++;
+      p += cs;
+      // a wide window of members under 1 KiB on average: the host cuts the file finer (wave-uniform)
+      if (!EMIT && d_dense && (n & 63) == 0 && p - start < n * CHAIN_DENSE) {
+        if (lane == 0) *d_dense = 1;
+        break;
+      }
+      if (cs < CHAIN_DENSE && p < we && !(p >= sb && p + 18 <= se)) {  // wave-uniform
+        __syncthreads();  // the reads of the old piece are done
+        sb = p & ~(int64_t)15;
+        se = min(sb + CHAIN_STAGE, L);
+#pragma unroll
+        for (int j = 0; j < CHAIN_STAGE / 1024; j++) {
+          const int so = j * 1024 + lane * 16;
+          if (sb + so < L)
+            *reinterpret_cast<uint4*>(stage + so) = *reinterpret_cast<const uint4*>(C + sb + so);
+        }
+        __syncthreads();
+      }
+    }
+  }
+  if (!EMIT && lane == 0)
+    wins[w] = ChainWin{start, start < 0 ? ws : p, n, usum, stop, hops && n <= CHAIN_HOPS ? 1 : 0};
+}
+
+// Parallel link check (dqc::link_ok): window w against the exit of the last earlier window that
+// took a block.  A stop anywhere but in the last window with bytes also goes to the repair, which
+// empties the windows behind it.
+__global__ void chain_link_kernel(const ChainWin* __restrict__ wins, int64_t nwin, int64_t W, int64_t L,
+                                  const unsigned long long* __restrict__ d_cstart,
+                                  int32_t* d_broken) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < 1 || w >= nwin) return;
+  const int64_t ws = chain_start_of(d_cstart, L) + w * W;
+  if (ws >= L) return;
+  // back over the windows that no block starts in: a member is at most 65536 bytes, so where the
+  // chain runs these are at most 65536 / W windows (16 at the finest W); only behind an early stop
+  // of the chain can a run of them be long, and that file goes to the repair anyway
+  int64_t t = w - 1;
+  while (t > 0 && wins[t].start < 0) t--;
+  if (!dqc::link_ok(wins[t].exit, wins[t].stop, wins[w], min(L, ws + W))) *d_broken = 1;
+}
+
+// Serial link check + repair (one lane), run only when chain_link found a broken link (a member
+// header inside payload was speculated, or the chain ends early): each link is O(1) unless the
+// speculation was wrong, in which case that window is walked again from the exact incoming
+// position; the walk meets the next window's speculated start or is repaired there in turn.
+__global__ void chain_fix_kernel(const uint8_t* __restrict__ C, int64_t L,
+                                 const unsigned long long* __restrict__ d_cstart,
+                                 ChainWin* __restrict__ wins, int64_t nwin, int64_t W,
+                                 const int32_t* __restrict__ d_broken,
+                                 const int32_t* __restrict__ d_dense) {
+  // a window that gave up (d_dense) leaves a partial walk and broken links all over: the host
+  // discards this pass, nothing is repaired
+  if (threadIdx.x != 0 || blockIdx.x != 0 || !*d_broken || (d_dense && *d_dense)) return;
+  const int64_t cs0 = chain_start_of(d_cstart, L);
+  int64_t in = wins[0].exit;
+  int32_t in_stop = wins[0].stop;
+  for (int64_t w = 1; w < nwin; w++) {
+    const int64_t ws = cs0 + w * W;
+    if (ws >= L) break;
+    const int64_t we = min(L, ws + W);
+    ChainWin& g = wins[w];
+    if (in_stop || in >= we) {  // the chain ended, or passes over this window
+      g = ChainWin{-1, in, 0, 0, 0, 0};
+      continue;
+    }
+    if (g.start != in) {
+      dqc::NoSink sink;
+      ChainWin r;
+      dqc::walk_window(C, L, in, we, &r, sink);
+      g = r;
+    }
+    in = g.exit;
+    in_stop = g.stop;
   }
 }
 
-__global__ void chain_serial_kernel(const uint8_t* __restrict__ C, int64_t L, int64_t start,
-                                    int64_t* __restrict__ blk_pos, int32_t* __restrict__ blk_csize,
-                                    int32_t* __restrict__ blk_usize, int64_t cap, int64_t* d_nblk,
-                                    int32_t* d_status) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int64_t p = start, n = 0;
-  while (p < L) {
-    int32_t cs;
-    if (!htsjdk_block(C, p, L, &cs)) break;
-    if (n >= cap) {
-      *d_status = ST_BAD_HEADER;
-      break;
-    }
-    blk_pos[n] = p;
-    blk_csize[n] = cs;
-    blk_usize[n] = ld32(C, p + cs - 4);
-    n++;
-    p += cs;
+__global__ void chain_totals_kernel(const ChainWin* __restrict__ wins, int64_t nwin,
+                                    int32_t* __restrict__ counts, unsigned long long* tot) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nwin) return;
+  const ChainWin g = wins[w];
+  counts[w] = (int32_t)g.count;
+  if (g.count) {
+    atomicAdd(&tot[0], (unsigned long long)g.count);
+    atomicAdd(&tot[1], (unsigned long long)g.usum);
   }
-  *d_nblk = n;
 }
 
 // ------------------------------------------------------------------ record guesser
@@ -398,15 +539,6 @@ __device__ int check_record_start(const uint8_t* U, int64_t ulen, int u_is_eof,
 }
 
 // ------------------------------------------------------------------ planning
-__device__ inline int64_t lower_bound_cand(const Cand* c, int64_t n, int64_t p) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (c[mid].pos < p) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 __device__ inline int64_t lower_bound_i64(const int64_t* a, int64_t n, int64_t v) {
   int64_t lo = 0, hi = n;
   while (lo < hi) {
@@ -441,15 +573,16 @@ __device__ inline int64_t block_of(const int64_t* uoff, int64_t nblk, int64_t x)
 
 // guessNextBGZFPos(p, end) over the candidate list (magic positions, in order), then the
 // BgzfBlockSource chain of the split: blocks [first, last] with pos <= split end.
-__global__ void plan_blocks_kernel(const Cand* __restrict__ cand, const int64_t* __restrict__ ncand,
-                                   const int64_t* __restrict__ blk_pos,
+__global__ void plan_blocks_kernel(CandList cl, const int64_t* __restrict__ blk_pos,
                                    const int32_t* __restrict__ blk_usize,
                                    const int64_t* __restrict__ uoff, const int64_t* __restrict__ d_nblk,
                                    SplitPlan* __restrict__ plans, int64_t nsplit) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nsplit) return;
   SplitPlan& P = plans[i];
-  const int64_t nc = *ncand, nb = *d_nblk;
+  const Cand* __restrict__ cand = cl.cand;
+  const int64_t nc = *cl.d_ncand, nb = *d_nblk;
+  const dqc::CandView V{cand, nc, cl.rng, cl.nrng, cl.L};
   P.first_blk = -1;
   P.rec_lin = -1;
   P.status = 0;
@@ -470,8 +603,12 @@ __global__ void plan_blocks_kernel(const Cand* __restrict__ cand, const int64_t*
     if (p > e) return;
     int64_t g = -1;
     for (;;) {
-      int64_t k = lower_bound_cand(cand, nc, p);
-      if (k >= nc) break;             // scan runs off the data -> null
+      int64_t k = dqc::cand_next(V, p, e);
+      if (k == dqc::CAND_UNKNOWN) {   // outside the scanned ranges: the host scans the whole file
+        *cl.need_full = 1;
+        return;
+      }
+      if (k >= nc) break;             // scan runs off the data (or to the split end) -> null
       const Cand c = cand[k];
       if (c.pos != p && c.pos >= e) break;  // :91 end check (skipped for the first position)
       if (c.valid == 1) {
@@ -2123,10 +2260,11 @@ void launch_bgzf_scan_listed(const uint8_t* C, int64_t n, int64_t L, Cand* big, 
                      s, C, n, L, big, chunk_counts, over_list, over_map);
 }
 
-void launch_gather_slots(const Cand* slots, const int32_t* counts, const int64_t* offs,
+void launch_gather_slots(const Cand* slots, int64_t stride, const int32_t* counts, const int64_t* offs,
                          int64_t nchunks, Cand* out, int64_t cap, const int32_t* over_map,
                          const Cand* big, hipStream_t s) {
-  hipLaunchKernelGGL(gather_slots_kernel, dim3((unsigned)nchunks), dim3(64), 0, s, slots, counts,
+  if (nchunks <= 0) return;
+  hipLaunchKernelGGL(gather_slots_kernel, dim3((unsigned)nchunks), dim3(64), 0, s, slots, stride, counts,
                      offs, nchunks, out, cap, over_map, big);
 }
 
@@ -2139,35 +2277,33 @@ void launch_exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, int64
   exclusive_scan<int64_t>(in, out, n, tmp, s);
 }
 
-void launch_valid_flags(const Cand* cand, const int64_t* ncand, int64_t cap, int32_t* flags,
+void launch_chain_start(const uint8_t* C, int64_t L, int32_t find_start, unsigned long long* d_cstart,
                         hipStream_t s) {
-  hipLaunchKernelGGL(valid_flags_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s,
-                     cand, ncand, flags);
+  (void)hipMemsetAsync(d_cstart, find_start ? 0xff : 0, sizeof(unsigned long long), s);
+  if (find_start && L > 0)
+    hipLaunchKernelGGL(chain_start_kernel, dim3(CS_K), dim3(256), 0, s, C, L, d_cstart);
 }
 
-void launch_chain2(const uint8_t* C, int64_t L, const Cand* cand, const int64_t* ncand, int64_t cap,
-                   const int64_t* voff, int64_t* blk_pos, int32_t* blk_csize, int32_t* blk_usize,
-                   int64_t blk_cap, int64_t* d_nblk, int32_t* d_broken, int32_t eof_in_buf,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, C, L, cand,
-                     ncand, voff, blk_pos, blk_csize, blk_usize, blk_cap, d_nblk, d_broken,
-                     eof_in_buf);
+void launch_chain_windows(const uint8_t* C, int64_t L, const unsigned long long* d_cstart,
+                          ChainWin* wins, int64_t nwin, int64_t W, int32_t* d_dense, uint16_t* hops,
+                          int32_t* d_broken, int32_t* counts, unsigned long long* tot, hipStream_t s) {
+  const unsigned g = (unsigned)((nwin + 255) / 256);
+  hipLaunchKernelGGL(chain_walk_kernel<false>, dim3((unsigned)nwin), dim3(64), 0, s, C, L, d_cstart,
+                     wins, nwin, W, d_dense, hops, nullptr, nullptr, nullptr, nullptr, 0);
+  hipLaunchKernelGGL(chain_link_kernel, dim3(g), dim3(256), 0, s, wins, nwin, W, L, d_cstart, d_broken);
+  hipLaunchKernelGGL(chain_fix_kernel, dim3(1), dim3(64), 0, s, C, L, d_cstart, wins, nwin, W, d_broken,
+                     d_dense);
+  hipLaunchKernelGGL(chain_totals_kernel, dim3(g), dim3(256), 0, s, wins, nwin, counts, tot);
 }
 
-// Chain start of a shard (the first valid candidate: the guesser's first block of its first
-// split) as a device min-reduction, plus a copy of the chain's first block position, so the host
-// reads both with the block count in one small copy.  out[0] = min valid pos (initialised to
-// all ones by the caller), out[1] = blk_pos[0].
-__global__ void chain_check_kernel(const Cand* __restrict__ cand, const int64_t* __restrict__ ncand,
-                                   const int64_t* __restrict__ blk_pos, const int64_t* __restrict__ d_nblk,
-                                   unsigned long long* __restrict__ out) {
-  const int64_t n = *ncand;
-  unsigned long long best = ~0ull;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    if (cand[i].valid == 1) best = min(best, (unsigned long long)cand[i].pos);
-  for (int o = 32; o >= 1; o >>= 1) best = min(best, (unsigned long long)__shfl_xor(best, o, 64));
-  if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&out[0], best);
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[1] = *d_nblk > 0 ? (unsigned long long)blk_pos[0] : ~0ull;
+void launch_chain_emit(const uint8_t* C, int64_t L, const unsigned long long* d_cstart,
+                       const ChainWin* wins, int64_t nwin, int64_t W, const uint16_t* hops,
+                       const int64_t* base, int64_t* blk_pos, int32_t* blk_csize, int32_t* blk_usize,
+                       int64_t cap, hipStream_t s) {
+  hipLaunchKernelGGL(chain_walk_kernel<true>, dim3((unsigned)nwin), dim3(64), 0, s, C, L, d_cstart,
+                     const_cast<ChainWin*>(wins), nwin, W, nullptr, const_cast<uint16_t*>(hops), base, blk_pos,
+                     blk_csize, blk_usize,
+                     cap);
 }
 
 // First block whose status is not ST_OK: a device min-reduction of the block index into out[0]
@@ -2183,12 +2319,6 @@ __global__ void first_bad_kernel(const int32_t* __restrict__ status, const int32
   if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(out, best);
 }
 
-void launch_chain_check(const Cand* cand, const int64_t* d_ncand, int64_t cap, const int64_t* blk_pos,
-                        const int64_t* d_nblk, unsigned long long* out, hipStream_t s) {
-  const unsigned g = (unsigned)std::min<int64_t>(1024, std::max<int64_t>(1, (cap + 255) / 256));
-  hipLaunchKernelGGL(chain_check_kernel, dim3(g), dim3(256), 0, s, cand, d_ncand, blk_pos, d_nblk, out);
-}
-
 void launch_first_bad(const int32_t* status, const int32_t* sel, int64_t n, unsigned long long* out,
                       hipStream_t s) {
   if (n <= 0) return;
@@ -2196,19 +2326,12 @@ void launch_first_bad(const int32_t* status, const int32_t* sel, int64_t n, unsi
   hipLaunchKernelGGL(first_bad_kernel, dim3(g), dim3(256), 0, s, status, sel, n, out);
 }
 
-void launch_chain_serial(const uint8_t* C, int64_t clen, int64_t start, int64_t* blk_pos,
-                         int32_t* blk_csize, int32_t* blk_usize, int64_t cap, int64_t* d_nblk,
-                         int32_t* d_status, hipStream_t s) {
-  hipLaunchKernelGGL(chain_serial_kernel, dim3(1), dim3(64), 0, s, C, clen, start, blk_pos,
-                     blk_csize, blk_usize, cap, d_nblk, d_status);
-}
-
-void launch_plan_blocks(const Cand* cand, const int64_t* d_ncand, const int64_t* blk_pos,
+void launch_plan_blocks(CandList cl, const int64_t* blk_pos,
                         const int32_t* blk_usize, const int64_t* uoff, const int64_t* d_nblk,
                         SplitPlan* plans, int64_t nsplit, hipStream_t s) {
   if (nsplit <= 0) return;
   hipLaunchKernelGGL(plan_blocks_kernel, dim3((unsigned)((nsplit + 63) / 64)), dim3(64), 0, s,
-                     cand, d_ncand, blk_pos, blk_usize, uoff, d_nblk, plans, nsplit);
+                     cl, blk_pos, blk_usize, uoff, d_nblk, plans, nsplit);
 }
 
 // Guesser at every position of the resident stream (BamRecordGuesserChecker's exhaustive check,

@@ -136,8 +136,7 @@ __global__ void text_cr_fills_kernel(const uint8_t* __restrict__ U, const int64_
 }
 
 // One thread per split: the line index range [k0, k1) it reads.
-__global__ void text_plan_kernel(const Cand* __restrict__ cand, const int64_t* __restrict__ ncand,
-                                 const int64_t* __restrict__ blk_pos,
+__global__ void text_plan_kernel(CandList cl, const int64_t* __restrict__ blk_pos,
                                  const int32_t* __restrict__ blk_us,
                                  const int64_t* __restrict__ uoff, int64_t nblk, int64_t flen,
                                  const uint8_t* __restrict__ U, int64_t ulen,
@@ -151,7 +150,9 @@ __global__ void text_plan_kernel(const Cand* __restrict__ cand, const int64_t* _
   P.b0 = -1;
   P.status = 0;
   P.bom = 0;
-  const int64_t s = P.split_start, e = P.split_end, nc = *ncand;
+  const Cand* __restrict__ cand = cl.cand;
+  const int64_t s = P.split_start, e = P.split_end, nc = *cl.d_ncand;
+  const dqc::CandView V{cand, nc, cl.rng, cl.nrng, cl.L};
   Lines L{U, ulen, term, nterm, 0};
   L.nl = nterm + ((nterm == 0 ? ulen > 0 : term[nterm - 1] + 1 < ulen) ? 1 : 0);
   // ---- BGZFCodec.createInputStream: guessNextBGZFPos(start, end) (BgzfBlockGuesser.java:76-149)
@@ -159,11 +160,10 @@ __global__ void text_plan_kernel(const Cand* __restrict__ cand, const int64_t* _
   {
     int64_t p = s;
     for (;;) {
-      int64_t lo = 0, hi = nc;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (cand[mid].pos < p) lo = mid + 1;
-        else hi = mid;
+      const int64_t lo = dqc::cand_next(V, p, e);
+      if (lo == dqc::CAND_UNKNOWN) {  // outside the scanned ranges: the host scans the whole file
+        *cl.need_full = 1;
+        return;
       }
       if (lo >= nc) break;
       const Cand c = cand[lo];
@@ -848,13 +848,13 @@ void launch_text_cr_fills(const uint8_t* U, const int64_t* uoff, const int32_t* 
                      uoff, blk_us, nblk, last_cr_fill);
 }
 
-void launch_text_plan(const Cand* cand, const int64_t* ncand, const int64_t* blk_pos,
+void launch_text_plan(CandList cl, const int64_t* blk_pos,
                       const int32_t* blk_us, const int64_t* uoff, int64_t nblk, int64_t flen,
                       const uint8_t* U, int64_t ulen, const int64_t* term, int64_t nterm,
                       const int64_t* last_cr_fill, TextPlan* plans, int64_t nsplit, hipStream_t s) {
   if (nsplit <= 0) return;
-  hipLaunchKernelGGL(text_plan_kernel, dim3((unsigned)((nsplit + 63) / 64)), dim3(64), 0, s, cand,
-                     ncand, blk_pos, blk_us, uoff, nblk, flen, U, ulen, term, nterm, last_cr_fill,
+  hipLaunchKernelGGL(text_plan_kernel, dim3((unsigned)((nsplit + 63) / 64)), dim3(64), 0, s, cl,
+                     blk_pos, blk_us, uoff, nblk, flen, U, ulen, term, nterm, last_cr_fill,
                      plans, nsplit);
 }
 
