@@ -103,6 +103,23 @@ constexpr int OUTCAP = 65536 + 24;  // + alignment shift (<= 15) + descriptor ov
 #ifndef DQ_RES_SLICE
 #define DQ_RES_SLICE 0
 #endif
+// DQ_RES_OCT (round 12, the product shape only): 1 = the first hop by groups of eight contiguous
+// bytes on the first WG / 128 waves (one bitmap word, one owner search and one 16-byte pointer
+// store per eight bytes; the second half-group inherits its incoming owner and that owner's
+// descriptor from the first); the other waves skip the first hop.  0: round 7's first hop.
+#ifndef DQ_RES_OCT
+#define DQ_RES_OCT 0
+#endif
+// DQ_RES_USTORE (round 12, with DQ_RES_OCT): 1 = the 16-byte U lines a batch completed are stored
+// by the waves that skip the next batch's first hop, not by waves 0-1 after the batch's steps.
+#ifndef DQ_RES_USTORE
+#define DQ_RES_USTORE 0
+#endif
+// DQ_RES_NOGUARD (round 12, the product shape only): 1 = a step stores every byte of its 512, with
+// no test against the resolved size: a byte at or past it is its own source and rewrites itself.
+#ifndef DQ_RES_NOGUARD
+#define DQ_RES_NOGUARD 1
+#endif
 constexpr int RES_NXT = DQ_RES_NB * DQ_RES_G * WG;  // resolve batch bytes (NB * G * WG)
 constexpr int NCARRY = (65536 + RES_NXT - 1) / RES_NXT + 1;  // batches of a block (carry slots)
 
@@ -1620,6 +1637,15 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
   const uint8_t* O = L.out + sh;
   const int head = min((16 - sh) & 15, rsize);  // bytes before the first 16-byte U boundary
   int32_t lines_done = 0;                       // 16-byte lines [head + 16k, +16) stored
+  int32_t lines_st = 0;                         // USTORE: those of them really stored
+  auto store_lines = [&](int32_t from, int32_t to, int32_t stride) {  // lines from, from + stride, ..
+    for (int32_t k = from; k < to; k += stride) {
+      const uint4 v = *reinterpret_cast<const uint4*>(O + head + 16 * k);
+      uint4* d = reinterpret_cast<uint4*>(dstU + head + 16 * k);
+      if (sflags & 2) st_nt(d, v);
+      else *d = v;
+    }
+  };
   // chunks of CH = G * WG bytes, thread t owns bytes [G t, G t + G) of each; NB chunks per batch;
   // a byte's chain may stop at any byte before its 512-byte step (the unit of the barriers in (b))
   constexpr int CH = G * WG;
@@ -1640,6 +1666,12 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
   constexpr bool HYB = G == 1 && NB == 4 && WG == 512 && !CSTEP && DQ_RES_QUAD != 0;
   constexpr int GK = HYB ? 1 : NB, GCH = HYB ? BATCH : CH;  // groups per thread, their stride
   static_assert(!(QUAD || HYB) || offsetof(LdsI, u.r.nxt) % 8 == 0, "a group's next pointers are one 64-bit word");
+  // OCT: HYB with the first hop by groups of eight bytes on the first BATCH / 512 waves
+  constexpr bool OCT = HYB && DQ_RES_OCT != 0;
+  static_assert(!OCT || offsetof(LdsI, u.r.nxt) % 16 == 0, "eight next pointers are one 128-bit store");
+  // USTORE: the waves that skip the first hop store the U lines of the batch before
+  constexpr bool USTORE = OCT && DQ_RES_USTORE != 0;
+  constexpr int UW0 = BATCH / 8;  // USTORE: the first thread of those waves
   constexpr bool INR = 65536 % BATCH == 0;  // no batch reaches past the largest block
   uint16_t* nxt = L.u.r.nxt;
   auto pack16 = [](int32_t lo, int32_t hi) {  // lo | hi << 16 of two 16-bit values: one v_perm
@@ -1665,6 +1697,99 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
   auto first_hop = [&](int32_t b0, int32_t cms, uint32_t cdesc, int32_t* fr, int32_t* xs,
                        bool& pending) {
     pending = false;
+    if constexpr (OCT) {
+      // Thread t of the first WG / 128 waves takes bytes 8t .. 8t + 7 of the batch, one byte of
+      // the bitmap word, as two half-groups in sequence; the other waves skip the first hop (a
+      // scalar branch).  The match live at the second half's byte 0 is a start there or the
+      // first half's B, "the last start at or before my byte 3", whose descriptor, carry rule
+      // (A < b0 -> cdesc) and length cut at rsize the first half holds in registers: the second
+      // half needs no bitmap or last_start read, no owner search, and reads the descriptor at
+      // its byte 0 without waiting for the first half.
+      if (__builtin_amdgcn_readfirstlane(wv) >= BATCH / 8 / 64) return;
+      const int32_t g0 = b0 + 8 * t;
+      const int w = g0 >> 6;
+      DQ_CHK(w >= 0 && w < 1024, CHK_K2_LAST);
+      const uint64_t m = bm64[w];
+      const int32_t ls = w ? (int32_t)zx16(L.u.r.last_start[w - 1]) : 0xffff;
+      const uint32_t bit = (uint32_t)g0 & 56u;
+      const uint64_t below = m & ~(~0ull << bit);  // the word's starts before the group
+      const int32_t prev = below ? (g0 | 63) - (int32_t)__clzll(below) : ls;
+      const uint32_t oct = (uint32_t)(m >> bit) & 255u;
+      // starts are >= 3 bytes apart: {0,3,6}, {0,3,7}, {0,4,7}, {1,4,7} and their subsets (past
+      // rsize the second half's bits are not the block's: the first half's nibble as before)
+      DQ_CHK(g0 >= rsize || (g0 + 4 >= rsize ? ((0x0317u >> (oct & 15u)) & 1u) != 0
+                                             : (oct & (oct >> 1 | oct >> 2)) == 0), CHK_K2_BM);
+      const uint32_t ld1 = load_desc(L, sh + g0 + 4);  // for a start at the second half's byte 0
+      typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+      const uint32_t gg = pack16(g0, g0);
+      uint32_t pk[4];  // the eight next pointers
+      // one half-group: its bytes' sources from A, the owner live at its byte 0 (descriptor dA,
+      // bytes from A to rsize remA, 0 for "no start yet"), and B, its highest start (else A),
+      // as in the group of four below; A, dA, remA leave as B's
+      auto half = [&](int h, uint32_t nib, int32_t& A, uint32_t& dA, int32_t& remA) {
+        const int32_t h0 = g0 + 4 * h;
+        const bool hasB = nib != 0;
+        const int32_t Bs = hasB ? h0 + 31 - (int32_t)__clz(nib) : A;
+        const uint32_t ldB = load_desc(L, sh + Bs);
+        const uint32_t dB = hasB ? ldB : dA;
+        const int32_t remB = hasB ? rsize - Bs : remA;
+        const int32_t D1A = (int32_t)(dA & 0x7fff), D1B = (int32_t)(dB & 0x7fff);  // D - 1
+        const int32_t limA = med3(remA, 0, (int32_t)(dA >> 15) + 3);
+        const int32_t limB = med3(remB, 0, (int32_t)(dB >> 15) + 3);
+        // A byte that copies has the source x - 1 - (D - 1), any other is its own source: with
+        // d = D - 1 or 0xffff two next pointers are one packed 16-bit subtraction from the pair
+        // of x - 1 (mod 2^16), and no byte's x or source is formed on its own.
+        const int32_t eA = h0 - A, eB = h0 - Bs;
+        uint32_t d4[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          // Byte 0 is A's and byte 3 B's by their definition.  A middle byte tries both, with no
+          // select of the owner: B's test fails for a byte before B (x - Bs wraps), and A's for
+          // a byte from B on, since A's match ends where the next one starts (without a start
+          // in the half B is A and the two tests are one).
+          const int32_t jA = eA + i, jB = eB + i;
+          const bool cA = i < 3 && (uint32_t)jA < (uint32_t)limA;
+          const bool cB = i > 0 && (uint32_t)jB < (uint32_t)limB;
+          DQ_CHK(!(cA && cB) || A == Bs, CHK_K2_SRC);
+          d4[i] = cB ? (uint32_t)D1B : cA ? (uint32_t)D1A : 0xffffu;
+          if (__builtin_expect(__any((cA && jA > D1A) || (cB && jB > D1B)), 0)) {
+            // past the first period of an overlapping match: see the group of four below
+            const int32_t ms = cB ? Bs : A, jj = cB ? jB : jA, D = (cB ? D1B : D1A) + 1;
+            const int32_t q = (int32_t)((float)jj * __builtin_amdgcn_rcpf((float)D));
+            int32_t r = jj - q * D;
+            r = r >= D ? r - D : r;
+            d4[i] = cA || cB ? (uint32_t)(h0 + i - 1 - (ms - D + r)) : 0xffffu;
+          }
+          DQ_CHK(!(cA || cB) || (h0 + i - 1 - (int32_t)d4[i] >= 0 && d4[i] < 32768u), CHK_K2_SRC);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {  // (packed at once: the first half's d die here)
+          const u16x2 xm1 = {(uint16_t)(4 * h + 2 * j - 1), (uint16_t)(4 * h + 2 * j)};
+          pk[2 * h + j] = __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, gg) + xm1 -
+                                                    __builtin_bit_cast(u16x2, pack16(d4[2 * j], d4[2 * j + 1]))));
+        }
+        A = Bs;
+        dA = dB;
+        remA = remB;
+      };
+      const uint32_t nib0 = oct & 15u, nib1 = oct >> 4;
+      int32_t A = (nib0 & 1u) ? g0 : prev;
+      // (an owner before the batch reads a stale descriptor, in range and unused: the carry's,
+      // or 0 for a match that ended before the batch, is taken instead)
+      const uint32_t ldA = load_desc(L, sh + A);
+      uint32_t dA = A < b0 ? cdesc : ldA;
+      int32_t remA = A == 0xffff ? 0 : rsize - A;
+      half(0, nib0, A, dA, remA);
+      const bool s1 = (nib1 & 1u) != 0;  // the one case in which the second half does not inherit
+      A = s1 ? g0 + 4 : A;
+      dA = s1 ? ld1 : dA;
+      remA = s1 ? rsize - (g0 + 4) : remA;
+      half(1, nib1, A, dA, remA);
+      DQ_CHK(8 * t + 7 < BATCH, CHK_K2_NXT);
+      const uint4 v = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+      __builtin_memcpy(__builtin_assume_aligned(nxt + 8 * t, 16), &v, 16);  // one ds_write_b128
+      return;
+    }
     if constexpr (QUAD || HYB) {
       // Bytes g0 .. g0 + 3 lie in one bitmap word and have at most two owners: A, the match live
       // at byte 0 (a start at g0, else the last start before the group), and B, the match live
@@ -1960,6 +2085,11 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     uint32_t raB[NE];
     bool pendB = false;
     uint32_t liveB = 0;
+    if constexpr (USTORE) {  // the lines of the batch before, final since its last step barrier
+      if (!(sflags & 1) && __builtin_amdgcn_readfirstlane(wv) >= UW0 / 64)
+        store_lines(lines_st + t - UW0, lines_done, WG - UW0);
+      lines_st = lines_done;
+    }
     if (more) first_hop(nbs, ncms, ncdesc, frB, xsB, pendB);
     const uint64_t tb1 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
     // (b) batch k's 512-byte steps in order: one LDS read + write per copied byte, one barrier.
@@ -1969,7 +2099,9 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     for (int k = 0; k < NB; k++) {
 #pragma unroll
       for (int j = 0; j < (CSTEP ? 1 : G); j++) {
-        const bool mine = CSTEP || ((G * t) >> 9) == j;
+        // (G == 1: a chunk is one step and every thread's byte is in it; the test t < 512 is an
+        // exec mask around each step's read and store that DQ_RES_NOGUARD drops too)
+        const bool mine = CSTEP || (G == 1 && DQ_RES_NOGUARD != 0) || ((G * t) >> 9) == j;
         const int32_t g0 = bs + k * CH + G * t;
         uint8_t v[G];
         if (mine)
@@ -2006,7 +2138,9 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
           if (mine)
 #pragma unroll
             for (int i = 0; i < G; i++)
-              if (g0 + i < rsize) L.out[sh + g0 + i] = v[i];  // a literal rewrites its own value
+              // a literal rewrites its own value; so does, without the test, a byte at or past
+              // rsize (its owner's length was cut at rsize: it is its own source, inside L.out)
+              if ((HYB && INR && DQ_RES_NOGUARD != 0) || g0 + i < rsize) L.out[sh + g0 + i] = v[i];
         }
         __syncthreads();
       }
@@ -2017,12 +2151,13 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
     const int32_t c1 = min(rsize, nbs);
     const int32_t lines_to = c1 >= head ? (c1 - head) / 16 : 0;
     if (!(sflags & 1)) {
-      for (int32_t k = lines_done + t; k < lines_to; k += WG) {
-        const uint4 v = *reinterpret_cast<const uint4*>(O + head + 16 * k);
-        uint4* d = reinterpret_cast<uint4*>(dstU + head + 16 * k);
-        if (sflags & 2) st_nt(d, v);
-        else *d = v;
-      }
+      if constexpr (!USTORE)
+        for (int32_t k = lines_done + t; k < lines_to; k += WG) {
+          const uint4 v = *reinterpret_cast<const uint4*>(O + head + 16 * k);
+          uint4* d = reinterpret_cast<uint4*>(dstU + head + 16 * k);
+          if (sflags & 2) st_nt(d, v);
+          else *d = v;
+        }
       lines_done = lines_to;
     }
     const uint64_t tb3 = TIMING ? __builtin_amdgcn_s_memtime() : 0;
@@ -2048,6 +2183,8 @@ __global__ __launch_bounds__(WG, WG / 128) void inflate_block_kernel(
       else *d = v;
     }
     lines_done = lines_to;
+  } else if constexpr (USTORE) {  // the last batch's lines
+    store_lines(lines_st + t, lines_done, WG);
   }
   // the CRC's constants, loaded ahead of the U tail stores and the barrier below (their latency
   // overlaps them): this thread's two table words, its slice's shift, and for thread 0 the

@@ -17,6 +17,10 @@ and batch; the rare modulo path (v_rcp_f32) is listed apart.  With -DDQ_RES_SLIC
 split up under scalar branches on its live mask: a read block per entry (one ds_read_u16), an
 update block per entry (one ds_write_b16) and the blocks of the mask tests between them, which
 are all that a round executes when no entry is live; the tool reports the VALU of each kind.
+With -DDQ_RES_OCT=1 only the first half of a workgroup's waves takes the first hop, and with
+-DDQ_RES_USTORE=1 only the other half stores U lines: blocks behind such a test of the wave's
+number are marked "lo waves" / "hi waves", and the last line gives the batch loop's VALU without
+the rounds for either half of the waves and their mean (per thread of a workgroup and batch).
 """
 import os
 import re
@@ -80,25 +84,42 @@ def resolve(ker):
             if best is None or len(body) > len(best[1]):
                 best = (name, body)
     a = next(i for i, l in enumerate(ker) if l.startswith(best[0] + ":"))
+    # -DDQ_RES_OCT=1: code that only the first waves of a workgroup run (the first hop: a scalar
+    # compare of the wave's number, v_readfirstlane, and a branch over it) or only the others (the
+    # U stores of -DDQ_RES_USTORE=1: the same compare folded into the exec mask) is split off
+    # into blocks of its own, marked "lo" and "hi"
     blocks, cur = [], None
     n = 0
-    for l in ker[a:]:
-        m = re.match(r"^(\.LBB\d+_\d+):", l)
+    text = [l.strip() for l in ker[a:]]
+    text = [x for x in text if x and (re.match(r"^\.LBB\d+_\d+:", x) or not x.startswith((";", ".")))]
+    gate, gate_end = None, None
+    for i, x in enumerate(text):
+        m = re.match(r"^(\.LBB\d+_\d+):", x)
         if m:
-            cur = [m.group(1), []]
+            if m.group(1) == gate_end:
+                gate, gate_end = None, None
+            cur = [m.group(1), [], gate]
             blocks.append(cur)
             continue
-        x = l.strip()
-        if x and not x.startswith((";", ".")):
-            cur[1].append(x)
-            n += 1
-            if n >= len(best[1]):
-                break
+        cur[1].append(x)
+        n += 1
+        if n >= len(best[1]):
+            break
+        if gate is None and re.match(r"s_cbranch_(scc1|execz)\s", x):
+            back = text[max(0, i - 8):i]
+            k = [j for j, y in enumerate(back) if re.match(r"s_cmp_gt_i32 s\d+, \d+$", y)]
+            if k and any(y.startswith("v_readfirstlane_b32") for y in text[max(0, i - 12):i]):
+                direct = back[k[-1] + 1:] == []  # the branch tests the compare itself: skips the upper waves
+                if direct or x.startswith("s_cbranch_execz"):
+                    gate, gate_end = ("lo" if direct else "hi"), x.split()[-1]
+                    cur = [cur[0] + "'", [], gate]
+                    blocks.append(cur)
     cnt = lambda b, op: sum(x.startswith(op) for x in b)  # noqa: E731
     state, tot, rounds = "first hop", {}, []
     split = {"read": [], "update": [], "test": []}
     print(f"resolve batch loop {best[0]}: {len(best[1])} instructions")
-    for name, b in blocks:
+    waves = {None: {}, "lo": {}, "hi": {}}  # kind -> VALU, by the waves that run the block
+    for name, b, gate in blocks:
         if not b:
             continue
         if state == "first hop" and cnt(b, "ds_read_u8"):
@@ -120,19 +141,29 @@ def resolve(ker):
         elif state == "steps" and cnt(b, "s_bitcmp1_b32") and not cnt(b, "ds_") and not cnt(b, "s_barrier"):
             kind = "round test"
             split["test"].append(cnt(b, "v_"))
-        elif state == "steps" and cnt(b, "global_store"):
+        elif cnt(b, "global_store") and (state == "steps" or gate == "hi"):
             kind = "U store"
         v, sa, d = cnt(b, "v_"), cnt(b, "s_"), cnt(b, "ds_")
         t = tot.setdefault(kind, [0, 0, 0, 0])
         for i, q in enumerate((v, sa, d, cnt(b, "v_ffbh"))):
             t[i] += q
+        waves[gate][kind] = waves[gate].get(kind, 0) + v
         if v + d > 3 or kind.startswith("round "):
             print(f"  {name:12s} {kind:12s} VALU {v:4d}  SALU {sa:4d}  DS {d:3d}  ffbh {cnt(b, 'v_ffbh')}"
-                  f"  ds_write_b64 {cnt(b, 'ds_write_b64')}  barriers {cnt(b, 's_barrier')}")
+                  f"  ds_write_b64 {cnt(b, 'ds_write_b64')}  barriers {cnt(b, 's_barrier')}"
+                  + (f"  {gate} waves" if gate else ""))
     for k, t in tot.items():
         print(f"{k:12s} VALU {t[0]:4d}  SALU {t[1]:4d}  DS {t[2]:3d}  ffbh {t[3]}")
     if rounds:
         print("jump rounds:", " ".join(map(str, rounds)), "VALU each")
+    # per thread and batch without the rounds (a wave runs as many as its chains need; the blocks
+    # above are their unrolled copies) and the modulo path: the lower and the upper half of the
+    # workgroup's waves, and their mean (the workgroup's sum per batch is that times its waves)
+    fixed = [k for k in tot if k not in ("jump round", "modulo path") and not k.startswith("round ")]
+    lo = sum(waves[None].get(k, 0) + waves["lo"].get(k, 0) for k in fixed)
+    hi = sum(waves[None].get(k, 0) + waves["hi"].get(k, 0) for k in fixed)
+    print(f"batch loop without rounds, VALU per thread and batch: lower waves {lo}, upper waves {hi}, "
+          f"mean {(lo + hi) / 2:.1f} ({', '.join(fixed)})")
     if split["read"] or split["update"]:
         r, u = max(split["read"] or [0]), max(split["update"] or [0])
         print(f"split rounds: {len(split['read'])} read blocks of at most {r} VALU (a read block holds the next "

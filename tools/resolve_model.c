@@ -12,7 +12,9 @@
 //   - rounds needed when the output is cut into ordered steps of S bytes (a match whose redirected
 //     source lies before its step's start is final at its step).
 //   - --nibbles: the start bits of every aligned group of four output bytes (a thread's group in
-//     the kernel's resolve: at most two matches own its bytes);
+//     the kernel's resolve: at most two matches own its bytes), and of every aligned group of
+//     eight (DQ_RES_OCT: a thread's two half-groups) with how often the second half's incoming
+//     owner is the first half's last one;
 //   - --pending: bytes still pending after the first hop (a copy whose source lies in the byte's
 //     own 512-byte step), per wave of 64 lanes holding one byte (64 bytes) or four contiguous
 //     bytes (256 bytes: the first and second half of a step) per lane.
@@ -161,6 +163,7 @@ typedef struct {
   long hops_lit, hops_lit_max, hops_win[8], win_rounds[8];
   long dag_steps, dag_need_prev, dag_depth_sum, dag_depth_max, dag_need_prev2;
   long nib[16], groups;
+  long oct[256], octs, oct_own, oct_inherit, oct_other, half_three;
   // [0] one byte per lane, [1] four per lane first half of a step, [2] second half
   long pw_waves[3], pw_bytes[3], pw_lanes[3], pw_empty[3], pend_bytes;
   // --rounds: per round (the last row collects the rounds past it) running waves, their pending
@@ -343,6 +346,31 @@ int main(int argc, char **argv) {
         S.nib[st[g] | st[g + 1] << 1 | st[g + 2] << 2 | st[g + 3] << 3]++;
         S.groups++;
       }
+      // aligned groups of eight (DQ_RES_OCT: one thread's two half-groups): the start bits, and
+      // whether the last start at or before byte 4 (the owner live at the second half's byte 0)
+      // is the last start at or before byte 3 (the first half's last owner, which it inherits)
+      {
+        static int32_t lst[70008];
+        int32_t run = -1;
+        for (int x = 0; x < ol + 8; x++) {
+          if (x < ol && st[x]) run = x;
+          lst[x] = run;
+        }
+        for (int g = 0; g < ol; g += 8) {
+          int b = 0;
+          for (int i = 0; i < 8; i++) b |= st[g + i] << i;
+          S.oct[b]++;
+          S.octs++;
+          if (st[g + 4]) S.oct_own++;
+          else if (lst[g + 4] == lst[g + 3]) S.oct_inherit++;
+          else S.oct_other++;
+          for (int h = 0; h < 8; h += 4) {  // distinct owners (last starts) of a half's four bytes
+            int n = 1;
+            for (int i = 1; i < 4; i++) n += lst[g + h + i] != lst[g + h + i - 1];
+            if (n > 2) S.half_three++;
+          }
+        }
+      }
       for (int w0 = 0; w0 < ol; w0 += 64) {  // one byte per lane
         int n = 0;
         for (int x = w0; x < w0 + 64; x++) n += pend[x];
@@ -487,6 +515,27 @@ int main(int argc, char **argv) {
     }
     printf("  no start %.1f %%, one start %.1f %%, two or more %.1f %%\n", 100.0 * S.nib[0] / S.groups,
            100.0 * one / S.groups, 100.0 * two / S.groups);
+    printf("aligned groups of eight output bytes: %ld; start bits:\n", S.octs);
+    long cnt[4] = {0, 0, 0, 0}, illegal = 0;
+    for (int i = 0; i < 256; i++) {
+      if (!S.oct[i]) continue;
+      int pc = 0;
+      char set[32] = "", *q = set;
+      for (int k = 0; k < 8; k++)
+        if (i >> k & 1) {
+          pc++;
+          q += sprintf(q, "%s%d", q == set ? "" : ",", k);
+        }
+      cnt[pc > 3 ? 3 : pc] += S.oct[i];
+      if (i & (i >> 1 | i >> 2)) illegal += S.oct[i];  // two starts less than 3 bytes apart
+      printf("  {%s}%*s %9ld  %6.2f %%\n", set, (int)(8 - (q - set)), "", S.oct[i], 100.0 * S.oct[i] / S.octs);
+    }
+    printf("  no start %.1f %%, one %.1f %%, two %.1f %%, three %.2f %%; groups with starts < 3 bytes apart: %ld\n",
+           100.0 * cnt[0] / S.octs, 100.0 * cnt[1] / S.octs, 100.0 * cnt[2] / S.octs, 100.0 * cnt[3] / S.octs, illegal);
+    printf("  owner live at the second half's byte 0: a start there %ld (%.1f %%), the first half's last owner %ld "
+           "(%.1f %%), neither %ld\n", S.oct_own, 100.0 * S.oct_own / S.octs, S.oct_inherit,
+           100.0 * S.oct_inherit / S.octs, S.oct_other);
+    printf("  half-groups whose four bytes have more than two owners: %ld\n", S.half_three);
   }
   if (opt_pend) {
     static const char *nm[3] = {"1 byte per lane (64 bytes)", "4 bytes per lane, first half of a step",
