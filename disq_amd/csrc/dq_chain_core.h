@@ -213,4 +213,19 @@ DQC_INLINE int64_t cand_next(const CandView& v, int64_t p, int64_t e) {
   return CAND_UNKNOWN;
 }
 
+// BgzfBlockSource's blocks of a split that ends at e, from its first block j (BgzfBlockSource.java:
+// 63-84: blocks while start <= split end): the last block of the table whose position is <= e,
+// never before j.  What `while (jl + 1 < nb && pos[jl + 1] <= e) jl++;` from jl = j gives on an
+// ascending table, by an upper-bound search in (j, nb): about log2(nb - j) loads instead of one
+// dependent load per block of the split.
+DQC_INLINE int64_t last_block_le(const int64_t* pos, int64_t nb, int64_t j, int64_t e) {
+  int64_t lo = j + 1, hi = nb;  // the first index in (j, nb) with pos > e lies in [lo, hi]
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (pos[mid] <= e) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
+}
+
 }  // namespace dqc

@@ -573,6 +573,12 @@ __device__ inline int64_t block_of(const int64_t* uoff, int64_t nblk, int64_t x)
 
 // guessNextBGZFPos(p, end) over the candidate list (magic positions, in order), then the
 // BgzfBlockSource chain of the split: blocks [first, last] with pos <= split end.
+// DQ_PLAN_SEARCH (round 13): 1 = the split's last block by dqc::last_block_le, an upper-bound
+// search of the block table (about 20 loads on the 12.5 GB file); 0 = the block-by-block loop of
+// the rounds before (about 1,470 dependent loads per split there, one thread per split).
+#ifndef DQ_PLAN_SEARCH
+#define DQ_PLAN_SEARCH 1
+#endif
 __global__ void plan_blocks_kernel(CandList cl, const int64_t* __restrict__ blk_pos,
                                    const int32_t* __restrict__ blk_usize,
                                    const int64_t* __restrict__ uoff, const int64_t* __restrict__ d_nblk,
@@ -631,8 +637,12 @@ __global__ void plan_blocks_kernel(CandList cl, const int64_t* __restrict__ blk_
     }
   }
   // BgzfBlockSource: blocks while start <= split end
+#if DQ_PLAN_SEARCH
+  const int64_t jl = dqc::last_block_le(blk_pos, nb, j, e);
+#else
   int64_t jl = j;
   while (jl + 1 < nb && blk_pos[jl + 1] <= e) jl++;
+#endif
   P.first_blk = j;
   P.u_lo = uoff[j];
   P.u_hi = uoff[jl] + blk_usize[jl];
@@ -645,31 +655,49 @@ __global__ void plan_blocks_kernel(CandList cl, const int64_t* __restrict__ blk_
 // atomic, and a workgroup stops once its next step starts past the current minimum -- every
 // position below the final minimum was checked by the workgroup that owns its step.
 // first_record_final_kernel then fills the plan (one thread per split).
+// DQ_FR_HEAD (round 13): the first DQ_FR_HEAD positions of every split are searched by one
+// workgroup per split in a launch of its own (K = 1, steps in order, done at the first step with a
+// hit), and the FR_K interleaved workgroups take the positions from there on: on short reads the
+// first record lies a few hundred bytes into the split's first block, so the second launch's
+// workgroups find the minimum already below their first step and leave without a check, where
+// every one of the sixteen used to run the ten-record check on 256 positions.  The minimum and the
+// "need more data" flag at it are the same: every position below the minimum is still checked by
+// the workgroup that owns its step.  0 = one launch of FR_K workgroups from the first position.
 constexpr int FR_K = 16;
+#ifndef DQ_FR_HEAD
+#define DQ_FR_HEAD 512
+#endif
+constexpr int64_t FR_SCAN = 10000000;
+static_assert(DQ_FR_HEAD % 256 == 0 && DQ_FR_HEAD >= 0 && DQ_FR_HEAD < FR_SCAN, "whole steps");
+// positions [u_lo + off0, u_lo + off1) of every split, K workgroups per split
+template <int K>
 __global__ __launch_bounds__(256) void first_record_kernel(
     const uint8_t* __restrict__ U, int64_t ulen, int32_t u_is_eof, const int32_t* __restrict__ ref_len,
-    int32_t n_ref, const SplitPlan* __restrict__ plans, int64_t nsplit,
+    int32_t n_ref, const SplitPlan* __restrict__ plans, int64_t nsplit, int64_t off0, int64_t off1,
     unsigned long long* __restrict__ best_all) {
   __shared__ unsigned long long cur;
-  const int64_t i = blockIdx.x / FR_K, k = blockIdx.x % FR_K;
+  const int64_t i = blockIdx.x / K, k = blockIdx.x % K;
   if (i >= nsplit) return;
   const SplitPlan& P = plans[i];
   if (P.first_blk < 0 || P.status != 0) return;
   unsigned long long* best = best_all + i;  // the minimum hit; best[nsplit]: a "need more data" seen
   const int64_t lo = P.u_lo;
-  const int64_t hi = min(P.u_hi, lo + (int64_t)10000000);
-  for (int64_t b = lo + 256 * k; b < hi; b += 256 * FR_K) {
+  const int64_t hi = min(P.u_hi, lo + off1);
+  for (int64_t b = lo + off0 + 256 * k; b < hi; b += 256 * K) {
     if (threadIdx.x == 0) cur = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const bool stop = (unsigned long long)b > cur;
     __syncthreads();
     if (stop) break;
     const int64_t v = b + threadIdx.x;
+    bool hit = false;
     if (v < hi) {
       const int r = check_record_start(U, ulen, u_is_eof, ref_len, n_ref, v);
-      if (r == 1 || r == 4) atomicMin(best, (unsigned long long)v);
+      hit = r == 1 || r == 4;
+      if (hit) atomicMin(best, (unsigned long long)v);
       if (r == 4) atomicOr(best + nsplit, 1ull);
     }
+    if (K == 1 && __syncthreads_or(hit)) break;  // steps in order: the minimum lies in this one
   }
 }
 
@@ -831,6 +859,13 @@ __global__ __launch_bounds__(NT) void seg_spec_kernel(const uint8_t* __restrict_
 #ifndef DQ_SPEC_SL
 #define DQ_SPEC_SL 16
 #endif
+// DQ_SPEC_BATCH (round 13, seg_spec_split_kernel): 1 = a wave's sub-segments first find their next
+// step with candidates (prefilter on LDS), then the wave runs the full check once for all of them;
+// 0 = each sub-segment runs the full check in the step its candidate appears in, so the wave goes
+// through the check's dependent loads once per sub-segment and false candidate, one after another.
+#ifndef DQ_SPEC_BATCH
+#define DQ_SPEC_BATCH 1
+#endif
 constexpr int SPEC_WIN = 1024;                   // candidates per staged window
 constexpr int SPEC_PIECES = (SPEC_WIN + 64) / 16;  // + one header's bytes past the last candidate
 __device__ __forceinline__ bool spec_prefilter(const __attribute__((address_space(3))) uint32_t* W,
@@ -924,7 +959,9 @@ __global__ __launch_bounds__(64) void seg_spec_lds_kernel(const uint8_t* __restr
 // the full check of its true start (three chained records, a dozen dependent round trips), so
 // several segments' checks in one wave overlap those latencies; the windows are 512 bytes.  Piece
 // k of sub-window u lands at LDS byte 1024 (k / SL) + 16 SL u + 16 (k % SL) (an LDS-DMA
-// instruction writes 16 bytes per lane at consecutive lane slots).
+// instruction writes 16 bytes per lane at consecutive lane slots).  The sub-segments' candidates
+// appear in different steps, and a wave that checks each where it appears runs the check up to
+// 64 / SL times in a row: DQ_SPEC_BATCH (above) runs it once for all of them.
 template <int SL>
 __global__ __launch_bounds__(64) void seg_spec_split_kernel(const uint8_t* __restrict__ U, int64_t ulen,
                                                             int32_t u_is_eof,
@@ -966,53 +1003,106 @@ __global__ __launch_bounds__(64) void seg_spec_split_kernel(const uint8_t* __res
       auto ldw = [&](int o) -> uint32_t {  // the dword at sub-window byte o (o % 4 == 0)
         return *(const __attribute__((address_space(3))) uint32_t*)(W + (o / SB) * 1024 + ub + (o % SB));
       };
+      // the header conditions of spec_prefilter on the staged bytes of candidate v (true where
+      // the header is not staged whole: the full check decides)
+      const int avail = 16 * np;
+      auto pre = [&](int64_t v) -> bool {
+        const int o = (int)(v - wb);
+        if (o + 36 > avail) return true;
+        if (v + 36 > ulen) return false;
+        const uint32_t sh = (uint32_t)(o & 3);
+        const int o4 = o & ~3;
+        uint32_t w[9], f[8];
+#pragma unroll
+        for (int k = 0; k < 9; k++) w[k] = ldw(o4 + 4 * k);
+#pragma unroll
+        for (int k = 0; k < 8; k++) f[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
+        const int32_t remaining = (int32_t)f[0], id = (int32_t)f[1], pos = (int32_t)f[2];
+        const int32_t nid = (int32_t)f[6], npos = (int32_t)f[7];
+        const int32_t name_len = (int32_t)(f[3] & 0xff);
+        const int32_t flags = (int32_t)(f[4] >> 16), n_cig = (int32_t)(f[4] & 0xffff);
+        const int32_t cig_len = (int32_t)((uint32_t)n_cig * 4u);
+        const int32_t l_seq = (int32_t)f[5];
+        const int32_t seq_len =
+            (int32_t)((uint32_t)l_seq + (uint32_t)((int32_t)((uint32_t)l_seq + 1u) / 2));
+        const int32_t zero_min =
+            (int32_t)((uint32_t)32 + (uint32_t)name_len + (uint32_t)cig_len + (uint32_t)seq_len);
+        bool pass = !(id < -1 || id >= n_ref || pos < -1) && !(nid < -1 || nid >= n_ref || npos < -1) &&
+                    name_len >= 2 && !((flags & 4) == 0 && (seq_len == 0 || n_cig == 0)) &&
+                    v + 36 + name_len <= ulen && remaining >= zero_min;
+        if (pass) {
+          const int t = o + 36 + name_len - 1;  // the name's NUL
+          if (t < avail && ((ldw(t & ~3) >> (8 * (t & 3))) & 0xff) != 0) pass = false;
+        }
+        if (pass && id >= 0 && pos > ref_len[id]) pass = false;
+        if (pass && nid >= 0 && npos > ref_len[nid]) pass = false;
+        return pass;
+      };
+#ifdef DQ_REC_TIMING
+      rt_[4] += 1;  // windows staged by this wave
+#endif
       bool scan = searching;
+#if DQ_SPEC_BATCH
+      // Finding apart from checking: every searching sub-segment steps through its window, LDS
+      // only, until a step holds candidates (its SL-bit share of the ballot); it then waits for
+      // the other sub-segments.  The full check runs once for the wave, each candidate of those
+      // steps on the lane that found it (ascending positions in lane order), and the lowest lane
+      // that chains is the segment's start.  A sub-segment whose candidates all fail goes on from
+      // its next step, and a further check runs with whatever the others have by then.
+      int64_t b = v0;
+      while (__any(scan)) {
+        bool need = scan, pass = false;
+        while (__any(need)) {
+          if (need) pass = b + ll < vend && pre(b + ll);
+          const uint64_t m = __ballot(need && pass) & umask;
+#ifdef DQ_REC_TIMING
+          rt_[5] += 1;  // prefilter steps of this wave
+#endif
+          if (need) {
+            if (m) {
+              need = false;  // this step's candidates go to the check
+            } else {
+              b += SL;
+              if (b >= vend) need = scan = false;  // this window is done
+            }
+          }
+        }
+        REC_T(1);
+        const bool cand = scan && pass;
+#ifdef DQ_REC_TIMING
+        rt_[3] += __any(cand) ? 1 : 0;
+        rt_[7] += __popcll(__ballot(cand));
+#endif
+        bool hit = false;
+        if (cand) hit = check_record_start<3>(U, ulen, u_is_eof, ref_len, n_ref, b + ll) == 1;
+        REC_T(2);
+        const uint64_t m = __ballot(hit) & umask;
+        if (scan) {
+          if (m) {
+            best = b + (__builtin_ctzll(m) - u * SL);
+            scan = false;
+            searching = false;
+          } else {
+            b += SL;
+            if (b >= vend) scan = false;  // this window is done
+          }
+        }
+      }
+#else
       for (int64_t b = v0; __any(scan); b += SL) {
         const int64_t v = b + ll;
         bool hit = false;
-        if (scan && v < vend) {
-          const int o = (int)(v - wb), avail = 16 * np;
-          bool pass = true;
-          if (o + 36 <= avail) {
-            if (v + 36 > ulen) {
-              pass = false;
-            } else {
-              const uint32_t sh = (uint32_t)(o & 3);
-              const int o4 = o & ~3;
-              uint32_t w[9], f[8];
-#pragma unroll
-              for (int k = 0; k < 9; k++) w[k] = ldw(o4 + 4 * k);
-#pragma unroll
-              for (int k = 0; k < 8; k++) f[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
-              const int32_t remaining = (int32_t)f[0], id = (int32_t)f[1], pos = (int32_t)f[2];
-              const int32_t nid = (int32_t)f[6], npos = (int32_t)f[7];
-              const int32_t name_len = (int32_t)(f[3] & 0xff);
-              const int32_t flags = (int32_t)(f[4] >> 16), n_cig = (int32_t)(f[4] & 0xffff);
-              const int32_t cig_len = (int32_t)((uint32_t)n_cig * 4u);
-              const int32_t l_seq = (int32_t)f[5];
-              const int32_t seq_len =
-                  (int32_t)((uint32_t)l_seq + (uint32_t)((int32_t)((uint32_t)l_seq + 1u) / 2));
-              const int32_t zero_min =
-                  (int32_t)((uint32_t)32 + (uint32_t)name_len + (uint32_t)cig_len + (uint32_t)seq_len);
-              pass = !(id < -1 || id >= n_ref || pos < -1) && !(nid < -1 || nid >= n_ref || npos < -1) &&
-                     name_len >= 2 && !((flags & 4) == 0 && (seq_len == 0 || n_cig == 0)) &&
-                     v + 36 + name_len <= ulen && remaining >= zero_min;
-              if (pass) {
-                const int t = o + 36 + name_len - 1;  // the name's NUL
-                if (t < avail && ((ldw(t & ~3) >> (8 * (t & 3))) & 0xff) != 0) pass = false;
-              }
-              if (pass && id >= 0 && pos > ref_len[id]) pass = false;
-              if (pass && nid >= 0 && npos > ref_len[nid]) pass = false;
-            }
-          }
-          REC_T(1);
+        const bool pass = scan && v < vend && pre(v);
 #ifdef DQ_REC_TIMING
-          rt_[3] += __any(pass) ? 1 : 0;
-          rt_[7] += __popcll(__ballot(pass));
+        rt_[5] += 1;
 #endif
-          if (pass) hit = check_record_start<3>(U, ulen, u_is_eof, ref_len, n_ref, v) == 1;
-          REC_T(2);
-        }
+        REC_T(1);
+#ifdef DQ_REC_TIMING
+        rt_[3] += __any(pass) ? 1 : 0;
+        rt_[7] += __popcll(__ballot(pass));
+#endif
+        if (pass) hit = check_record_start<3>(U, ulen, u_is_eof, ref_len, n_ref, v) == 1;
+        REC_T(2);
         const uint64_t m = __ballot(hit) & umask;
         if (scan && m) {
           best = b + (__builtin_ctzll(m) - u * SL);
@@ -1021,6 +1111,7 @@ __global__ __launch_bounds__(64) void seg_spec_split_kernel(const uint8_t* __res
         }
         if (b + SL >= vend) scan = false;  // this window is done
       }
+#endif
       if (searching) {
         v0 = vend;
         searching = v0 < se;
@@ -2357,8 +2448,11 @@ void launch_first_record(const uint8_t* U, int64_t ulen, int32_t u_is_eof, const
   if (nsplit <= 0) return;
   (void)hipMemsetAsync(best, 0xff, 8 * (size_t)nsplit, s);       // minima: all ones
   (void)hipMemsetAsync(best + nsplit, 0, 8 * (size_t)nsplit, s);  // "need more data" flags
-  hipLaunchKernelGGL(first_record_kernel, dim3((unsigned)(nsplit * FR_K)), dim3(256), 0, s, U, ulen,
-                     u_is_eof, ref_len, n_ref, plans, nsplit, best);
+  if (DQ_FR_HEAD > 0)
+    hipLaunchKernelGGL(first_record_kernel<1>, dim3((unsigned)nsplit), dim3(256), 0, s, U, ulen,
+                       u_is_eof, ref_len, n_ref, plans, nsplit, (int64_t)0, (int64_t)DQ_FR_HEAD, best);
+  hipLaunchKernelGGL(first_record_kernel<FR_K>, dim3((unsigned)(nsplit * FR_K)), dim3(256), 0, s, U, ulen,
+                     u_is_eof, ref_len, n_ref, plans, nsplit, (int64_t)DQ_FR_HEAD, FR_SCAN, best);
   hipLaunchKernelGGL(first_record_final_kernel, dim3((unsigned)((nsplit + 63) / 64)), dim3(64), 0, s,
                      U, ulen, u_is_eof, ref_len, n_ref, blk_pos, uoff, d_nblk, plans, nsplit, best);
 }
@@ -2398,8 +2492,10 @@ void launch_seg_spec(const uint8_t* U, int64_t ulen, int32_t u_is_eof, int64_t c
     (void)hipStreamSynchronize(s);
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_rec_tim), sizeof(h));
     fprintf(stderr, "[dq] seg_spec cycles summed over waves: staging=%.3g prefilter=%.3g full_checks=%.3g; "
-            "steps with a full check %.3g, candidates passing the prefilter %.3g, segments %lld\n",
-            (double)h[0], (double)h[1], (double)h[2], (double)h[3], (double)h[7], (long long)nseg);
+            "windows staged %.3g, prefilter steps %.3g, full checks run by a wave %.3g, candidates "
+            "passing the prefilter %.3g, segments %lld\n",
+            (double)h[0], (double)h[1], (double)h[2], (double)h[4], (double)h[5], (double)h[3], (double)h[7],
+            (long long)nseg);
     const unsigned long long z[8] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rec_tim), z, sizeof(z));
   }

@@ -3,11 +3,12 @@
 # parity and adversarial GPU tests under libdisq_gpu_checked.so; the session fails on any failed
 # device check (tests/conftest.py).  usage: tools/gpu_checked_tests.sh TAG [test files]
 # (default: the inflate, parity, adversarial, chunk, text, deflate, hand-off, resolve-group,
-# resolve-round, .bai, .tbi, SAM, header pre-pass, record-edge and coordinate-edge tests)
+# resolve-round, .bai, .tbi, SAM, header pre-pass, record-edge, coordinate-edge, batched-speculation
+# and plan-edge tests)
 set -eo pipefail
 tag=$1
 shift
-tests=${@:-tests/test_inflate_codes.py tests/test_gpu_parity.py tests/test_adversarial.py tests/test_chunk_decode.py tests/test_text_gpu.py tests/test_deflate_gpu.py tests/test_tail_handoff.py tests/test_resolve_groups.py tests/test_resolve_rounds.py tests/test_bai.py tests/test_tbi.py tests/test_sam_gpu.py tests/test_header_prepass.py tests/test_header_prepass_counts.py tests/test_record_edges.py tests/test_coord_edges.py}
+tests=${@:-tests/test_inflate_codes.py tests/test_gpu_parity.py tests/test_adversarial.py tests/test_chunk_decode.py tests/test_text_gpu.py tests/test_deflate_gpu.py tests/test_tail_handoff.py tests/test_resolve_groups.py tests/test_resolve_rounds.py tests/test_bai.py tests/test_tbi.py tests/test_sam_gpu.py tests/test_header_prepass.py tests/test_header_prepass_counts.py tests/test_record_edges.py tests/test_coord_edges.py tests/test_spec_batched.py tests/test_plan_edges_gpu.py}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp DQ_GPU_LIB=$PWD/disq_amd/_build/libdisq_gpu_checked.so
